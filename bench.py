@@ -9,15 +9,23 @@ moves, examples and re-rooting on device. One bench "step" = one self-play itera
 simulation (select -> network -> expand/backup) on every game plus the move commit of every
 game whose search is done. The games are first brought to a steady state (--prefill
 iterations: games at every stage, trees at their steady size — the synthetic input), then W
-warm-up steps, then exactly K timed steps; after them an extended window (--window
-iterations, default ~68 K finished games) reports capacity events, finished examples drained
-+ gathered, and tree sizes.
+warm-up steps, then exactly K timed steps. A plain run stops there: it prints the result
+line with the headline (`value`, `ms_per_step` = milliseconds per timed step).
 
-Secondary objects in the same line (N = 1 only): config 2 (env-step-only random policy,
-fused rollout kernel, board-steps/s), config 5 (4 players, 16,384 games, 400 simulations)
-and config 4's per-GPU shard (32,768 games, 1,600 simulations), each at steady state with
-its window statistics and CPU baselines (the oracle, a scalar C port of the reference, on
-one host core and on every granted core).
+--dump-outputs DIR (self-play workloads): after the timed steps, what the timed path left
+for its caller goes to DIR/<name>.npy (dump_selfplay_outputs: per-tree headers, root
+statistics, the last leaf evaluation and the finished examples, the large ones as a fixed
+seeded sample). Deals, network and draws are seeded, so two runs with the same arguments
+write the same arrays.
+
+--full adds everything else. After the timed steps an extended window (--window
+iterations, default ~68 K finished games) reports capacity events, finished examples drained
++ gathered, and tree sizes; the network kernel is timed on its own (roofline block), and the
+CPU baselines run (the oracle, a scalar C port of the reference, on one host core and on
+every granted core). Secondary objects in the same line (N = 1 only): config 2
+(env-step-only random policy, fused rollout kernel, board-steps/s), config 5 (4 players,
+16,384 games, 400 simulations) and config 4's per-GPU shard (32,768 games, 1,600
+simulations), each at steady state with its window statistics and CPU baselines.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; for N>1 one rank per GPU, either
 launched by torch.distributed.run (WORLD_SIZE set: it must equal N) or, when started
@@ -268,14 +276,16 @@ def stagger_marks(stagger, groups, sims, ratio):
 
 
 def run_selfplay(cfg, rank, world, dev, dist, steps, warmup, prefill, window, seed, node_boards=-1,
-                 stagger=0, groups=16, mem_gib=0.0, on_steady=None, net_path=None):
+                 stagger=0, groups=16, mem_gib=0.0, on_steady=None, net_path=None, full=True, dump_dir=None):
     """Self-play at one BASELINE config: B games per GPU (shard board_base = rank * B), one
     MCTS simulation per game per iteration, leaves evaluated by the fused SplendorNNet kernel
     (fp32, random init), moves committed on device. `prefill` untimed iterations bring the
     games to a steady state, `warmup` more, then exactly `steps` timed iterations (barrier +
-    synchronize on both sides, max over ranks); then `window` iterations whose statistics
-    (capacity events, games, moves) are reported, ending with the finished examples drained
-    and all-gathered over RCCL; symmetry expansion is timed after it.
+    synchronize on both sides, max over ranks). dump_dir: rank 0 then writes what the timed
+    path left for its caller (dump_selfplay_outputs). full: then `window` iterations whose
+    statistics (capacity events, games, moves) are reported, ending with the finished examples
+    drained and all-gathered over RCCL; symmetry expansion and the network
+    kernel alone are timed after it. Without `full` the result holds the timed steps only.
 
     stagger: the B games are dealt together, so without it they share one game phase for
     many generations and the per-iteration cost oscillates with it (config 3: 0.56-0.95 ms
@@ -350,10 +360,31 @@ def run_selfplay(cfg, rank, world, dev, dist, steps, warmup, prefill, window, se
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     iter_ms_events = ev0.elapsed_time(ev1) / steps
+    res = {"elapsed": elapsed, "iter_ms_events": iter_ms_events, "prefill": prefill, "prefill_s": prefill_s,
+           "stagger": {"iterations": stagger, "groups": groups}}
+    if not (full or dump_dir):
+        del sp, ev, net
+        return res
+    # the examples the timed steps finished are drained here for the dump, or when some were
+    # lost (the queue holds one game per tree, so many timed steps can overflow it: the loss
+    # is reported, and the window's drains do not raise for it)
+    ex_local = 0
+    lost = sp.dropped_examples() - sp._dropped_seen
+    if lost:
+        log(f"{cfg}: {lost} finished examples of the timed steps did not fit the example queue")
+    if dump_dir or lost:
+        ex = sp.drain(allow_drops=True)
+        ex_local = int(ex["board"].shape[0])
+        if dump_dir and rank == 0:
+            log(f"{cfg}: timed {steps} iterations, {elapsed:.2f} s; writing outputs to {dump_dir}")
+            dump_selfplay_outputs(sp, ev, None if lost else ex, dump_dir, seed)
+        del ex
+    if not full:
+        del sp, ev, net
+        return res
     # extended window: capacity events, games, examples drained + gathered
     c0 = sp.counter_snapshot()
     pool0 = sp.pool_state()
-    ex_local = 0
     tw = time.perf_counter()
     done = 0
     log(f"{cfg}: timed {steps} iterations, {elapsed:.2f} s; window {window}")
@@ -433,31 +464,94 @@ def run_selfplay(cfg, rank, world, dev, dist, steps, warmup, prefill, window, se
             "device_bytes": sp.device_bytes,
             "pool_free_at_end": {"node_pages": pool["free_node_pages"], "of": pool["node_pages"],
                                  "edge_pages": pool["free_edge_pages"], "of_edge": pool["edge_pages"]}}
-    res = {"elapsed": elapsed, "iter_ms_events": iter_ms_events, "window": delta, "tree": tree,
-           "prefill": prefill, "prefill_s": prefill_s, "stagger": {"iterations": stagger, "groups": groups},
-           "symmetry": {"examples": nsym, "variants": int(sym["board"].shape[0]) if sym else 0, "s": sym_s},
-           "nn_kernel_us": nn_us, "nn_leaf_fraction": nn_leaf_frac}
+    res.update({"window": delta, "tree": tree,
+                "symmetry": {"examples": nsym, "variants": int(sym["board"].shape[0]) if sym else 0, "s": sym_s},
+                "nn_kernel_us": nn_us, "nn_leaf_fraction": nn_leaf_frac})
     del sp, ev, net
     return res
 
 
+# per-tree header fields of tree_headers.npy, in column order: the game and search state a
+# caller reads with SelfPlay.headers() (slot counts and collection state are left out: they
+# depend on the order in which trees take pages from the shared pools)
+DUMP_HEADER_FIELDS = ("player", "episode_step", "move_no", "game_no", "games_done", "moves", "sims_done",
+                      "budget", "full", "depth", "depth_sum", "sims_backed")
+DUMP_TREES = 1024        # trees sampled for the wide per-tree arrays
+DUMP_EXAMPLES = 2048     # finished examples sampled
+
+
+def dump_selfplay_outputs(sp, ev, ex, out_dir, seed):
+    """--dump-outputs: what the timed path left for its caller after the last timed step, as
+    out_dir/<name>.npy (float64, the float32 device arrays as float32; ~25 MB):
+      tree_headers [B, len(DUMP_HEADER_FIELDS)]  SelfPlay.headers(), every tree
+      tree_sample [DUMP_TREES]                   the trees (seeded choice) of the arrays below
+      root_counts / root_qsa / root_probs [.., 409]   SelfPlay.root_stats() (without its q, the
+                                                 root node's own value: a root that was just
+                                                 created holds none yet)
+      leaf_state [.., R, 7], leaf_pi [.., 409], leaf_v [.., n]   the last iteration's leaves and
+                                                 the network's output rows for them
+      example_meta [E, 4] (board id, game, move, player), example_board / _pi / _valids /
+      _winner / _scdiff / _surprise              `ex` = the examples the timed steps finished
+                                                 (SelfPlay.drain()): a seeded choice of
+                                                 DUMP_EXAMPLES after sorting by (board id, game,
+                                                 move), since queue order follows the order in
+                                                 which games end within an iteration; left out
+                                                 when ex is None (examples were lost)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+
+    def save(name, a, dtype=np.float64):
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+    h = sp.headers()
+    save("tree_headers", np.stack([h[f].astype(np.float64) for f in DUMP_HEADER_FIELDS], axis=1))
+    trees = np.sort(rng.choice(sp.B, size=min(sp.B, DUMP_TREES), replace=False))
+    save("tree_sample", trees)
+    t = torch.from_numpy(trees).to(sp.e.device)
+    counts, qsa, probs, _ = sp.root_stats()
+    for name, a in (("root_counts", counts), ("root_qsa", qsa), ("root_probs", probs)):
+        save(name, a[t])
+    del counts, qsa, probs
+    save("leaf_state", sp.leaf_state[t], np.float32)
+    save("leaf_pi", ev.pi_buf[t], np.float32)
+    save("leaf_v", ev.v_buf[t], np.float32)
+    if ex is None or not ex["meta"].shape[0]:
+        return
+    meta = ex["meta"].cpu().numpy()
+    order = np.lexsort((meta[:, 2], meta[:, 1], meta[:, 0]))
+    pick = np.sort(rng.choice(order.size, size=min(order.size, DUMP_EXAMPLES), replace=False))
+    idx = torch.from_numpy(order[pick]).to(sp.e.device)
+    save("example_meta", meta[order[pick]])
+    bits = np.unpackbits(ex["valids"][idx].cpu().numpy().view(np.uint8), axis=1, bitorder="little")
+    save("example_valids", bits[:, :ex["pi"].shape[1]], np.float32)
+    save("example_board", ex["board"][idx], np.float32)
+    save("example_pi", ex["pi"][idx], np.float32)
+    for k in ("winner", "scdiff", "surprise"):
+        save("example_" + k, ex[k][idx])
+
+
 def selfplay_record(cfg, r, world, steps, warmup):
-    """The JSON object of one self-play config."""
+    """The JSON object of one self-play config (the window, tree and kernel entries: run_selfplay
+    with `full`)."""
     n, B, sims = CONFIGS[cfg]
-    fl = nn_flops_per_eval(n) * B
-    return {"workload": f"{cfg}: {n}-player batched self-play, {B} games per GPU, numMCTSSims={sims}, genbu "
-                        "search args, SplendorNNet fp32 leaf eval (random init), device move commit",
-            "value": world * B * steps / r["elapsed"], "unit": "rollouts/s (MCTS simulations)",
-            "n_gpus": world, "global_games": world * B,
-            "ms_per_iteration": r["elapsed"] / steps * 1e3, "ms_per_iteration_events": r["iter_ms_events"],
-            "steps": steps, "warmup": warmup, "prefill_iterations": r["prefill"], "prefill_s": r["prefill_s"],
-            "phase_stagger": r["stagger"],
-            "window": r["window"], "tree": r["tree"], "symmetry_expansion": r["symmetry"],
-            # every search ran on the reference's table (no prune / reset / unexpanded leaf in the
-            # window; withdrawals repeat a simulation exactly): False marks a non-conforming record
-            "reference_table": not any(r["window"].get(k, 0) for k in ("prunes", "resets", "unexpanded")),
-            "nn_leaf_fraction": r["nn_leaf_fraction"],
-            "network_kernel": _network_kernel(n, B, r["nn_kernel_us"])}
+    rec = {"workload": f"{cfg}: {n}-player batched self-play, {B} games per GPU, numMCTSSims={sims}, genbu "
+                       "search args, SplendorNNet fp32 leaf eval (random init), device move commit",
+           "value": world * B * steps / r["elapsed"], "unit": "rollouts/s (MCTS simulations)",
+           "n_gpus": world, "global_games": world * B,
+           "ms_per_iteration": r["elapsed"] / steps * 1e3, "ms_per_iteration_events": r["iter_ms_events"],
+           "steps": steps, "warmup": warmup, "prefill_iterations": r["prefill"], "prefill_s": r["prefill_s"],
+           "phase_stagger": r["stagger"]}
+    if "window" not in r:
+        return rec
+    rec.update({
+        "window": r["window"], "tree": r["tree"], "symmetry_expansion": r["symmetry"],
+        # every search ran on the reference's table (no prune / reset / unexpanded leaf in the
+        # window; withdrawals repeat a simulation exactly): False marks a non-conforming record
+        "reference_table": not any(r["window"].get(k, 0) for k in ("prunes", "resets", "unexpanded")),
+        "nn_leaf_fraction": r["nn_leaf_fraction"],
+        "network_kernel": _network_kernel(n, B, r["nn_kernel_us"])})
+    return rec
 
 
 def _network_kernel(n, B, us):
@@ -688,7 +782,7 @@ def dry_run(args, rank, world):
                 "window": {"examples_drained": k, "examples_gathered": gathered, **PHASES[cfg]}}
     head = "config3" if args.workload in ("all", "selfplay") else args.workload
     extra = {}
-    if args.workload == "all" and world > 1 and not args.no_secondary:
+    if args.full and args.workload == "all" and world > 1 and not args.no_secondary:
         extra["config4_shard"] = record("config4")
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": None, "unit": "rollouts/s (MCTS simulations)",
@@ -707,19 +801,24 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000, help="timed self-play iterations (headline)")
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true", help="also the statistics window, the network kernel alone "
+                    "and the roofline block, the CPU baselines and the secondary configs (2 / 5 / 4); without "
+                    "it a run does the headline's timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="self-play workloads: after the timed "
+                    "steps write what they computed to DIR/<name>.npy (dump_selfplay_outputs)")
     ap.add_argument("--prefill", type=int, default=None, help="untimed iterations to the steady state first "
                     "(default: the workload's, PHASES)")
     ap.add_argument("--stagger", type=int, default=None, help="prefill iterations over which the games' phases "
                     "are spread (run_selfplay; ~ the mean game length: config 3 ~4,800 iterations)")
-    ap.add_argument("--window", type=int, default=None, help="statistics window after the timed steps")
+    ap.add_argument("--window", type=int, default=None, help="--full: statistics window after the timed steps")
     ap.add_argument("--boards", type=int, default=32768, help="env workload: boards per GPU")
     ap.add_argument("--players", type=int, default=2, help="env workload: players")
     ap.add_argument("--seed", type=int, default=0x5EED)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baselines")
     ap.add_argument("--traffic-json", default=None)
     ap.add_argument("--workload", choices=("all", "selfplay", "env", "config3", "config4", "config5"), default="all",
-                    help="all: config-3 headline + config 2/5/4 objects (N=1); selfplay = config3 alone")
-    ap.add_argument("--no-secondary", action="store_true", help="all: the headline only")
+                    help="all: config-3 headline (+ config 2/5/4 objects with --full, N=1); selfplay = config3 alone")
+    ap.add_argument("--no-secondary", action="store_true", help="all with --full: the headline only")
     ap.add_argument("--chunk", type=int, default=100, help="env: moves per rollout launch")
     ap.add_argument("--env-steps", type=int, default=1000, help="config-2 object: timed moves")
     ap.add_argument("--c5-prefill", type=int, default=PHASES["config5"]["prefill"])
@@ -740,6 +839,10 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs and args.workload == "env":
+        # (its untimed clock ramp runs for a fixed time, not a fixed number of moves, so the
+        # boards two runs end on differ)
+        ap.error("--dump-outputs covers the self-play workloads (not --workload env)")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))    # the parent never touches the GPU
@@ -763,7 +866,7 @@ def main():
 
     if args.workload == "env":
         rec = run_env(args, rank, world, dev, dist, args.steps, args.warmup,
-                      cpu=rank == 0 and world == 1 and not args.no_cpu_baseline)
+                      cpu=args.full and rank == 0 and world == 1 and not args.no_cpu_baseline)
         if rank == 0:
             print(json.dumps({"metric": METRIC, "value": rec["value"], "unit": rec["unit"], "n_gpus": world,
                               "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"],
@@ -781,12 +884,13 @@ def main():
     n, B, sims = CONFIGS[head]
     ph = {k: (getattr(args, k) if getattr(args, k) is not None else v) for k, v in PHASES[head].items()}
     r = run_selfplay(head, rank, world, dev, dist, args.steps, args.warmup, ph["prefill"], ph["window"], args.seed,
-                     args.node_boards, stagger=ph["stagger"], mem_gib=args.mem_gib, net_path=args.net)
+                     args.node_boards, stagger=ph["stagger"], mem_gib=args.mem_gib, net_path=args.net,
+                     full=args.full, dump_dir=args.dump_outputs)
     rec = selfplay_record(head, r, world, args.steps, args.warmup)
     torch.cuda.empty_cache()
     extra = {}
-    secondary = args.workload == "all" and not args.no_secondary
-    cpu_ok = rank == 0 and world == 1 and not args.no_cpu_baseline
+    secondary = args.full and args.workload == "all" and not args.no_secondary
+    cpu_ok = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if cpu_ok:
         rec["cpu_baseline"] = cpu_baseline_selfplay(n, args.seed, sims)
     if secondary and world > 1:
@@ -821,7 +925,8 @@ def main():
                        "numMCTSSims": sims, "prefill_iterations": ph["prefill"],
                        "phase_stagger_iterations": ph["stagger"],
                        "parallelism": f"dp{world} (game shards; RCCL all-gather of examples)"},
-            "roofline": selfplay_roofline(rec, n, rec["tree"]["leaf_depth_mean"]),
+            "full": args.full,
+            **({"roofline": selfplay_roofline(rec, n, rec["tree"]["leaf_depth_mean"])} if args.full else {}),
             "cpu_baseline": cpu,
             "selfplay": rec,
             **extra,

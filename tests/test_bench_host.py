@@ -71,7 +71,13 @@ def test_config4_multi_rank_dry_run(workload):
     on every rank (65,536 games in all) with its own prefill / stagger / window, and its
     window's example all-gather runs over the ranks (gloo here, RCCL on the GPUs)."""
     import json
-    r = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--dry-run"])
+    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--dry-run"]
+    if workload == "all":
+        plain = _run_bench(argv)                        # the secondary objects are behind --full
+        assert plain.returncode == 0, plain.stderr[-2000:]
+        assert "config4_shard" not in json.loads([ln for ln in plain.stdout.splitlines() if ln.startswith("{")][-1])
+        argv.append("--full")
+    r = _run_bench(argv)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     c4 = out["selfplay"] if workload == "config4" else out["config4_shard"]
@@ -85,6 +91,56 @@ def test_config4_multi_rank_dry_run(workload):
 def test_phase_defaults_per_workload(bench):
     assert bench.PHASES["config3"] == dict(prefill=6000, stagger=4800, window=10000)
     assert bench.PHASES["config4"]["prefill"] == 84000 and bench.PHASES["config5"]["prefill"] == 40000
+
+
+def test_dump_outputs_ignores_queue_order(bench, tmp_path):
+    """--dump-outputs (host part, stub engine on the CPU): the arrays are float32 / float64
+    .npy files, and the example sample does not depend on the order in which the finished
+    examples stand in the queue (games that end in one iteration take their slots in any
+    order): two queue orders give the same files."""
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    from splendor.mcts import HDR_DTYPE
+    B, n, R, E = 96, 2, 56, 5000
+    g = torch.Generator().manual_seed(1)
+    hdr = np.zeros(B, HDR_DTYPE)
+    for f in bench.DUMP_HEADER_FIELDS:
+        hdr[f] = np.arange(B) * 3 + len(f)
+    sp = SimpleNamespace(B=B, e=SimpleNamespace(device=torch.device("cpu")), headers=lambda: hdr,
+                         root_stats=lambda: (torch.arange(B * 409).reshape(B, 409),
+                                             torch.rand((B, 409), generator=g, dtype=torch.float64),
+                                             torch.rand((B, 409), generator=g, dtype=torch.float64),
+                                             torch.rand((B, n), generator=g, dtype=torch.float64)),
+                         leaf_state=torch.randint(0, 9, (B, R, 7), generator=g).to(torch.int8))
+    ev = SimpleNamespace(pi_buf=torch.rand((B, 409), generator=g), v_buf=torch.rand((B, n), generator=g))
+    meta = torch.stack([torch.arange(E) // 50, torch.arange(E) % 50 // 10, torch.arange(E) % 10,
+                        torch.arange(E) % n], 1).to(torch.int32)
+    ex = {"meta": meta, "board": torch.randint(0, 9, (E, R, 7), generator=g).to(torch.int8),
+          "pi": torch.rand((E, 409), generator=g), "valids": torch.randint(-2**62, 2**62, (E, 7), generator=g),
+          "winner": torch.rand((E, n), generator=g), "scdiff": torch.randint(-9, 9, (E, n), generator=g).to(torch.int32),
+          "surprise": torch.rand((E, n), generator=g)}
+    perm = torch.randperm(E, generator=g)
+    for d, e in (("a", ex), ("b", {k: v[perm] for k, v in ex.items()})):
+        g.manual_seed(2)                                   # (the stub's root_stats draw from g)
+        bench.dump_selfplay_outputs(sp, ev, e, str(tmp_path / d), 0x5EED)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "example_pi.npy" in names and "root_counts.npy" in names
+    total = 0
+    for nm in names:
+        a, b = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), nm
+        total += a.nbytes
+    assert total <= 64 << 20
+    m = np.load(tmp_path / "a" / "example_meta.npy")
+    assert m.shape == (bench.DUMP_EXAMPLES, 4)
+    keys = m[:, 0] * 1e6 + m[:, 1] * 1e3 + m[:, 2]
+    assert (np.diff(keys) > 0).all()                       # sorted by (board id, game, move), no repeats
+    v = np.load(tmp_path / "a" / "example_valids.npy")
+    row = int(np.flatnonzero((meta[:, :3].numpy() == m[0, :3]).all(1))[0])
+    word, bit = divmod(70, 64)
+    assert v.shape == (bench.DUMP_EXAMPLES, 409) and v[0, 70] == (int(ex["valids"][row, word]) >> bit) & 1
+    assert np.load(tmp_path / "a" / "tree_headers.npy").shape == (B, len(bench.DUMP_HEADER_FIELDS))
 
 
 def test_window_counters_are_wrap_safe():

@@ -7,15 +7,15 @@
 #
 #   tests     pytest -m gpu (one process; per-test timeout)           -> gpurun_out/gpu_tests.log
 #   smoke     __graft_entry__.smoke()                                  -> gpurun_out/smoke.log
-#   bench     the default bench line (headline + secondary objects)    -> gpurun_out/bench.json
+#   bench     the whole bench line (--full: headline + secondary objects) -> $OUT/bench.json
 #   selfplay  the config-3 headline alone                              -> gpurun_out/selfplay.json
 #   trace     config-3 kernel trace + stats (rocprofv3)                -> gpurun_out/prof_sp/ (or prof_<TREE>)
 #   split     per-iteration kernel split from the trace (needs trace)  -> gpurun_out/split.txt
 #   spikes    the slowest launches of each kernel and their iterations (needs trace) -> gpurun_out/spikes.json
 #   pmc       PMC passes over the self-play kernels (pmc_selfplay.sh)  -> gpurun_out/pmc_sp/
 #   nn        full-batch network trace + HBM counters (nn_fullbatch.sh) -> gpurun_out/nnfb/
-#   trainprior  tools/train_prior.py: a few Coach.learn iterations -> gpurun_out/trained_2p.pt,
-#             then the config-3 headline on those weights -> gpurun_out/selfplay_trained.json
+#   trainprior  tools/train_prior.py: a few Coach.learn iterations -> $OUT/trained_2p.pt,
+#             then the config-3 headline on those weights -> $OUT/selfplay_trained.json
 #   accuracy  the fused network vs float64 on 4,096 positions at 2p and 4p (nn_accuracy.py)
 #             -> gpurun_out/nn_accuracy.jsonl
 #   ab        interleaved A/B of the product against each V in $AB: ablib/lib<V>.so, or a whole
@@ -34,6 +34,10 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 ROUND=${ROUND:-r06}
+# the steps below read the window statistics and per-kernel figures of the bench line: --full
+EXTRA="--full ${EXTRA:-}"
+OUT=${OUT:-out}                                            # output folder of the bench and trainprior steps
+mkdir -p "$OUT"
 TR=${TREE:-sp}                                             # trace / split / spikes: TREE=<V> traces
 TB=bench.py; [ -n "${TREE:-}" ] && TB="ablib/$TREE/bench.py"  # the older tree ablib/<V>/ instead
 step() {
@@ -45,7 +49,7 @@ step() {
     smoke)
         timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 ;;
     bench)
-        timeout -k 10 900 python3 -u bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err ;;
+        timeout -k 10 900 python3 -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
     selfplay)
         timeout -k 10 300 python3 -u bench.py --workload selfplay --no-cpu-baseline ${EXTRA:-} \
             > gpurun_out/selfplay.json 2> gpurun_out/selfplay.err ;;
@@ -64,10 +68,10 @@ step() {
     nn)
         timeout -k 10 400 bash tools/nn_fullbatch.sh "$ROUND" > gpurun_out/nnfb.log 2>&1 ;;
     trainprior)
-        timeout -k 10 900 python3 -u tools/train_prior.py gpurun_out/trained_2p.pt "${ITERS:-4}" "${GAMES:-4096}" \
-            > gpurun_out/train_prior.jsonl 2> gpurun_out/train_prior.err &&
-        timeout -k 10 300 python3 -u bench.py --workload selfplay --no-cpu-baseline --net gpurun_out/trained_2p.pt \
-            > gpurun_out/selfplay_trained.json 2> gpurun_out/selfplay_trained.err ;;
+        timeout -k 10 900 python3 -u tools/train_prior.py "$OUT/trained_2p.pt" "${ITERS:-4}" "${GAMES:-4096}" \
+            > "$OUT/train_prior.jsonl" 2> "$OUT/train_prior.err" &&
+        timeout -k 10 300 python3 -u bench.py --full --workload selfplay --no-cpu-baseline --net "$OUT/trained_2p.pt" \
+            > "$OUT/selfplay_trained.json" 2> "$OUT/selfplay_trained.err" ;;
     accuracy)
         rm -f gpurun_out/nn_accuracy.jsonl
         for np_ in 2 4; do
