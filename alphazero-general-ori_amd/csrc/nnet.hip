@@ -25,6 +25,9 @@
 //     (spl_nn_forward in splendor_amd.h), each lane's B operand one coalesced 16-byte load,
 //     prefetched a chunk ahead in a register ring; the next layer's ring is issued behind the
 //     last MFMA of the current one; barriers wait for LDS only.
+//   * Opt-in reduced modes (spl_nn_forward_mode; template parameter PR of k_nn_forward): only the
+//     leading 2 or 1 parts of every operand are multiplied, and only those parts are loaded.
+//     PR = 3 is everything above, unchanged.
 #include <hip/hip_runtime.h>
 
 #include "../../include/splendor_amd.h"
@@ -239,10 +242,12 @@ __device__ __forceinline__ float get_split(const SplitAct *s, int row, int col) 
     return h + (m + l);
 }
 
-// weight-part ring of a per-leaf GEMM: PF chunks (32 k) x NC column tiles x 3 parts
-template <int NC, int PF>
+// weight-part ring of a per-leaf GEMM: PF chunks (32 k) x NC column tiles x 3 parts, of which
+// the leading Q (the precision mode's parts, spl_nn_forward_mode) are loaded
+template <int NC, int PF, int QP = 3>
 struct RingL {
     static constexpr int P = PF;
+    static constexpr int Q = QP;
     bf16x8 b[PF][NC][3];
 };
 // column tile j of a per-leaf layer: tile min(c0 + j cstep, ctot - 1) (a clamped tile is
@@ -263,7 +268,7 @@ __device__ __forceinline__ void ringl_load(const float *__restrict__ ws, int c0,
 #pragma unroll
         for (int p = 0; p < RG::P; p++)
 #pragma unroll
-            for (int q = 0; q < 3; q++) r.b[p][j][q] = w[((p < C ? p : C - 1) * 3 + q) * 64];
+            for (int q = 0; q < RG::Q; q++) r.b[p][j][q] = w[((p < C ? p : C - 1) * 3 + q) * 64];
     }
 }
 // per-leaf GEMM on v_mfma_f32_16x16x32_bf16: RT row tiles of 16 leaves x NC column tiles
@@ -272,10 +277,13 @@ __device__ __forceinline__ void ringl_load(const float *__restrict__ ws, int c0,
 // 8 (l / 16) .. + 7); the ring holds the first chunks (ringl_load); next() runs after the last
 // MFMA is issued. Each (column, row) tile keeps two accumulators, the hi x hi products and
 // the five smaller ones, added at the end. Unrolled and branch-free like gemm_split.
+// Reduced modes (RG::Q leading parts per operand): Q = 2 keeps hi x hi in its accumulator and
+// puts hi x mid + mid x hi into the small one, Q = 1 has the hi x hi products alone; afetch
+// fills only the first Q parts.
 template <int NC, int RT, int C, class RG, class AF, class NX>
 __device__ __forceinline__ void gemm_leaf(const float *__restrict__ ws, int c0, int cstep, RG &r, AF afetch,
                                           f32x4 (*acc)[2], NX next) {
-    constexpr int PF = RG::P;
+    constexpr int PF = RG::P, Q = RG::Q;
     const bf16x8 *w[NC];
 #pragma unroll
     for (int j = 0; j < NC; j++) w[j] = tilel<C>(ws, c0, cstep, 1 << 30, j);
@@ -297,14 +305,18 @@ __device__ __forceinline__ void gemm_leaf(const float *__restrict__ ws, int c0, 
             const bf16x8 b0 = r.b[c % PF][j][0], b1 = r.b[c % PF][j][1], b2 = r.b[c % PF][j][2];
             if (c + PF < C)
 #pragma unroll
-                for (int q = 0; q < 3; q++) r.b[c % PF][j][q] = w[j][((c + PF) * 3 + q) * 64];
+                for (int q = 0; q < Q; q++) r.b[c % PF][j][q] = w[j][((c + PF) * 3 + q) * 64];
 #pragma unroll
             for (int t = 0; t < RT; t++) {
-                acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][2], b0, acl[j][t], 0, 0, 0);
-                acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], b1, acl[j][t], 0, 0, 0);
-                acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], b2, acl[j][t], 0, 0, 0);
-                acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], b0, acl[j][t], 0, 0, 0);
-                acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], b1, acl[j][t], 0, 0, 0);
+                if constexpr (Q == 3) {
+                    acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][2], b0, acl[j][t], 0, 0, 0);
+                    acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], b1, acl[j][t], 0, 0, 0);
+                    acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], b2, acl[j][t], 0, 0, 0);
+                }
+                if constexpr (Q >= 2) {
+                    acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], b0, acl[j][t], 0, 0, 0);
+                    acl[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], b1, acl[j][t], 0, 0, 0);
+                }
                 acc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], b0, acc[j][t], 0, 0, 0);
             }
         }
@@ -314,10 +326,12 @@ __device__ __forceinline__ void gemm_leaf(const float *__restrict__ ws, int c0, 
     }
     next();
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (Q >= 2) {
 #pragma unroll
-    for (int j = 0; j < NC; j++)
+        for (int j = 0; j < NC; j++)
 #pragma unroll
-        for (int t = 0; t < RT; t++) acc[j][t] += acl[j][t];
+            for (int t = 0; t < RT; t++) acc[j][t] += acl[j][t];
+    }
 }
 struct NoNext {
     __device__ void operator()() const {}
@@ -426,7 +440,11 @@ __device__ __forceinline__ int nn_list_rows(const int32_t *__restrict__ count, i
     return base;
 }
 
-template <int NP>
+// PR (spl_nn_forward_mode): the leading bf16 parts of every matrix-product operand that enter
+// the MFMAs, 3 (SPL_NN_F32: the six products above), 2 (SPL_NN_BF16X2: hi hi, hi mid, mid hi) or
+// 1 (SPL_NN_BF16: hi hi); parts that are not multiplied are not loaded (weights) or not read
+// (split activations). Everything between the GEMMs is f32 on their untruncated outputs.
+template <int NP, int PR>
 // one workgroup per CU (LDS) = 2 waves per SIMD: the register budget is 256, and without
 // saying so the scheduler sinks the prefetched weight loads next to their MFMAs
 // idx / count (optional): the kernel evaluates the search's NN leaves as k_leaf_mask lists
@@ -454,7 +472,8 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     char *ring = lds + Nt::XR;                             // per-column weight stages (2 buffers)
     float *biasL = reinterpret_cast<float *>(SB0);         // [4][128] per-column biases (until dense1d_4)
     // wave 7 (it owns no board column) fills the weight stages: stage S's split weight chunks
-    // into buffer S & 1, one 1 KB fragment (column block b, part p, chunk c) per instruction
+    // into buffer S & 1, one 1 KB fragment (column block b, part p < PR, chunk c) per instruction
+    // (the slots of the parts a reduced mode leaves out stay unwritten and unread)
     auto load_stage = [&](auto s_const) {
         constexpr int S = decltype(s_const)::value;
         if constexpr (S < NSTG) {
@@ -466,7 +485,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int b = 0; b < 4; b++)
 #pragma unroll
-                    for (int p = 0; p < 3; p++)
+                    for (int p = 0; p < PR; p++)
                         glds16(src + ((b * C + C0 + j) * 3 + p) * 1024, dst + ((j * 4 + b) * 3 + p) * 1024);
         }
     };
@@ -547,9 +566,9 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
         if (count && w == 0 && lane < nb) rowv[lane] = (int)rowin(lane);   // (after the input loads)
     } else {
-        // stage 0 landed (stage 1's 12 x nc fragments may stay in flight): vmcnt(N) encoded as
+        // stage 0 landed (stage 1's 4 PR x nc fragments may stay in flight): vmcnt(N) encoded as
         // vmcnt[3:0] | vmcnt[5:4] << 14, expcnt and lgkmcnt at their maxima (no wait)
-        constexpr int N1 = 12 * Nt::stg_nc(1);
+        constexpr int N1 = 4 * PR * Nt::stg_nc(1);
         static_assert(N1 < 64, "vmcnt range");
         __builtin_amdgcn_s_waitcnt((N1 & 15) | ((N1 >> 4) << 14) | (7 << 4) | (15 << 8));
     }
@@ -574,7 +593,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bf16x8 *w4 = reinterpret_cast<const bf16x8 *>(W + Nt::soff(4)) + (size_t)(2 * bp4 * 4 * C4 + kq4 * C4) * 3 * 64 + lane;
     constexpr int W4B = 4 * C4 * 3 * 64;                   // the next block's fragments (bf16x8)
     bf16x8 r4[PF4][2][3];
-    RingL<1, 2> ring1;                                     // per-leaf layers' weight ring
+    RingL<1, 2, PR> ring1;                                 // per-leaf layers' weight ring
     auto stage = [&](auto s_const) {
         constexpr int S = decltype(s_const)::value;
         constexpr int L = Nt::stg_layer(S), C0 = Nt::stg_c0(S), NC = Nt::stg_nc(S);
@@ -615,17 +634,23 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int b = 0; b < 4; b++) {
                     const char *f = buf + (j * 4 + b) * 3 * 1024;
                     const bf16x8 wh = *reinterpret_cast<const bf16x8 *>(f);
-                    const bf16x8 wm = *reinterpret_cast<const bf16x8 *>(f + 1024);
-                    const bf16x8 wl = *reinterpret_cast<const bf16x8 *>(f + 2048);
-                    if constexpr (L == 0) {
-                        Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, Ys[b], 0, 0, 0);
+                    if constexpr (PR == 3) {
+                        const bf16x8 wm = *reinterpret_cast<const bf16x8 *>(f + 1024);
+                        const bf16x8 wl = *reinterpret_cast<const bf16x8 *>(f + 2048);
+                        if constexpr (L == 0) {
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, Ys[b], 0, 0, 0);
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, Ys[b], 0, 0, 0);
+                        } else {
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, Ys[b], 0, 0, 0);
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bm, Ys[b], 0, 0, 0);
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bl, Ys[b], 0, 0, 0);
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, Ys[b], 0, 0, 0);
+                            Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bm, Ys[b], 0, 0, 0);
+                        }
+                    } else if constexpr (PR == 2) {        // (PR == 1: the hi x hi product alone)
+                        const bf16x8 wm = *reinterpret_cast<const bf16x8 *>(f + 1024);
                         Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, Ys[b], 0, 0, 0);
-                    } else {
-                        Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, Ys[b], 0, 0, 0);
-                        Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bm, Ys[b], 0, 0, 0);
-                        Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bl, Ys[b], 0, 0, 0);
-                        Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, bh, Ys[b], 0, 0, 0);
-                        Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bm, Ys[b], 0, 0, 0);
+                        if constexpr (L != 0) Ys[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bm, Ys[b], 0, 0, 0);
                     }
                     Y[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bh, Y[b], 0, 0, 0);
                 }
@@ -639,7 +664,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int b = 0; b < 2; b++)
 #pragma unroll
-                    for (int q = 0; q < 3; q++) r4[c][b][q] = w4[b * W4B + (c * 3 + q) * 64];
+                    for (int q = 0; q < PR; q++) r4[c][b][q] = w4[b * W4B + (c * 3 + q) * 64];
         } else if (w == 7) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stage S + 1 landed
         }
@@ -737,13 +762,13 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // bias of this lane's column in tile ct of a per-leaf layer (0-padded to whole tiles), read
     // before the layer's GEMM (vmcnt retires loads in order)
     auto bias16 = [&](int layer, int ct) { return W[Nt::boff(layer) + 16 * ct + acc16_col()]; };
-    // A operand of a split source: the three planes' 8 bf16 at (row, k) of this lane
+    // A operand of a split source: the (leading PR) planes' 8 bf16 at (row, k) of this lane
     auto split_fetch = [&](const SplitAct *src, int koff) {
         return [=](int t, int c, bf16x8 &a0, bf16x8 &a1, bf16x8 &a2) {
             const int row = 16 * t + (lane & 15), k = koff + 32 * c + 8 * (lane >> 4);
             a0 = *reinterpret_cast<const bf16x8 *>(&src->p[0][row][k]);
-            a1 = *reinterpret_cast<const bf16x8 *>(&src->p[1][row][k]);
-            a2 = *reinterpret_cast<const bf16x8 *>(&src->p[2][row][k]);
+            if constexpr (PR >= 2) a1 = *reinterpret_cast<const bf16x8 *>(&src->p[1][row][k]);
+            if constexpr (PR == 3) a2 = *reinterpret_cast<const bf16x8 *>(&src->p[2][row][k]);
         };
     };
     // epilogue: tile j (column tile ct) of both row tiles into dst, columns < nmax
@@ -786,7 +811,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int b = 0; b < 2; b++)
 #pragma unroll
-                for (int q = 0; q < 3; q++) {
+                for (int q = 0; q < PR; q++) {
                     wv[b][q] = r4[c % PF4][b][q];
                     if (c + PF4 < C4) r4[c % PF4][b][q] = w4[b * W4B + ((c + PF4) * 3 + q) * 64];
                 }
@@ -795,11 +820,15 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             split8(F8{ld4(zp), ld4(zp + 4)}, bh, bm, bl);
 #pragma unroll
             for (int b = 0; b < 2; b++) {
-                Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][2], bh, Ds[b], 0, 0, 0);
-                Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][1], bm, Ds[b], 0, 0, 0);
-                Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][0], bl, Ds[b], 0, 0, 0);
-                Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][1], bh, Ds[b], 0, 0, 0);
-                Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][0], bm, Ds[b], 0, 0, 0);
+                if constexpr (PR == 3) {
+                    Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][2], bh, Ds[b], 0, 0, 0);
+                    Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][1], bm, Ds[b], 0, 0, 0);
+                    Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][0], bl, Ds[b], 0, 0, 0);
+                }
+                if constexpr (PR >= 2) {
+                    Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][1], bh, Ds[b], 0, 0, 0);
+                    Ds[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][0], bm, Ds[b], 0, 0, 0);
+                }
                 D[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wv[b][0], bh, D[b], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -890,7 +919,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // ---- heads: PI[0] -> SB1, V[0] -> SB2 (no activation); wave w: column tile w of both
     constexpr int CT = ntiles16(ACT);      // PI[1] column tiles
     static_assert(CT > 24 && CT <= 32, "PI[1] tiles: 3 or 4 per wave");
-    RingL<4, 1> ring4;
+    RingL<4, 1, PR> ring4;
     {
         const float bp = bias16(9, w), bv = bias16(11, w);
         gemm_leaf<1, 2, 4>(W + Nt::soff(9), w, 8, ring1, split_fetch(SB0, 0), a16, ringn(11));
@@ -993,6 +1022,23 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 inline int check_launch() { return hipGetLastError() == hipSuccess ? 0 : SPL_EDEVICE; }
 
+// the instantiation of (players 2 .. 4, precision mode 0 .. 2: 3 - mode parts per operand)
+template <int NP>
+const void *nn_kernel_np(int precision) {
+    switch (precision) {
+        case SPL_NN_F32: return reinterpret_cast<const void *>(&k_nn_forward<NP, 3>);
+        case SPL_NN_BF16X2: return reinterpret_cast<const void *>(&k_nn_forward<NP, 2>);
+        default: return reinterpret_cast<const void *>(&k_nn_forward<NP, 1>);
+    }
+}
+inline const void *nn_kernel(int n_players, int precision) {
+    switch (n_players) {
+        case 2: return nn_kernel_np<2>(precision);
+        case 3: return nn_kernel_np<3>(precision);
+        default: return nn_kernel_np<4>(precision);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1022,32 +1068,37 @@ int spl_nn_packed_floats(int n_players) {
 
 static int launch_nn(int n_players, int B, const int8_t *leaf_state, const uint64_t *leaf_mask,
                      const float *packed_weights, float *pi, float *v, const int32_t *idx, const int32_t *count,
-                     void *hs) {
+                     int precision, void *hs) {
     if (n_players < 2 || n_players > 4 || B < 0 || (B && (!leaf_state || !leaf_mask || !packed_weights || !pi || !v)))
         return SPL_EINVAL;
+    if (precision < SPL_NN_F32 || precision > SPL_NN_BF16) return SPL_EINVAL;
     if (!B) return 0;
-    const dim3 grid((unsigned)((B + ML - 1) / ML));
-    switch (n_players) {
-        case 2: hipLaunchKernelGGL(k_nn_forward<2>, grid, dim3(NNT), 0, (hipStream_t)hs, B, leaf_state, leaf_mask,
-                                   packed_weights, pi, v, idx, count); break;
-        case 3: hipLaunchKernelGGL(k_nn_forward<3>, grid, dim3(NNT), 0, (hipStream_t)hs, B, leaf_state, leaf_mask,
-                                   packed_weights, pi, v, idx, count); break;
-        default: hipLaunchKernelGGL(k_nn_forward<4>, grid, dim3(NNT), 0, (hipStream_t)hs, B, leaf_state, leaf_mask,
-                                    packed_weights, pi, v, idx, count); break;
-    }
+    const void *kernel = nn_kernel(n_players, precision);
+    void *args[] = {&B, &leaf_state, &leaf_mask, &packed_weights, &pi, &v, &idx, &count};
+    if (hipLaunchKernel(kernel, dim3((unsigned)((B + ML - 1) / ML)), dim3(NNT), args, 0, (hipStream_t)hs) != hipSuccess)
+        return SPL_EDEVICE;
     return check_launch();
 }
 
 int spl_nn_forward(int n_players, int B, const int8_t *leaf_state, const uint64_t *leaf_mask,
                    const float *packed_weights, float *pi, float *v, void *hs) {
-    return launch_nn(n_players, B, leaf_state, leaf_mask, packed_weights, pi, v, nullptr, nullptr, hs);
+    return launch_nn(n_players, B, leaf_state, leaf_mask, packed_weights, pi, v, nullptr, nullptr, SPL_NN_F32, hs);
 }
 
 int spl_nn_forward_indexed(int n_players, int B, const int8_t *leaf_state, const uint64_t *leaf_mask,
                            const int32_t *leaf_index, const int32_t *leaf_count, const float *packed_weights,
                            float *pi, float *v, void *hs) {
     if (!leaf_index || !leaf_count || reinterpret_cast<uintptr_t>(leaf_count) % 16) return SPL_EINVAL;
-    return launch_nn(n_players, B, leaf_state, leaf_mask, packed_weights, pi, v, leaf_index, leaf_count, hs);
+    return launch_nn(n_players, B, leaf_state, leaf_mask, packed_weights, pi, v, leaf_index, leaf_count, SPL_NN_F32,
+                     hs);
+}
+
+int spl_nn_forward_mode(int n_players, int B, const int8_t *leaf_state, const uint64_t *leaf_mask,
+                        const int32_t *leaf_index, const int32_t *leaf_count, const float *packed_weights,
+                        float *pi, float *v, int precision, void *hs) {
+    if (!leaf_index != !leaf_count || (leaf_count && reinterpret_cast<uintptr_t>(leaf_count) % 16)) return SPL_EINVAL;
+    return launch_nn(n_players, B, leaf_state, leaf_mask, packed_weights, pi, v, leaf_index, leaf_count, precision,
+                     hs);
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@ import torch
 
 from .env import ACTIONS, unpack_mask
 from .mcts import BatchedMCTS
-from .search import evaluator_for
+from .search import evaluator_for, nn_precision_arg
 
 PASS = 408
 DEAL_STREAM = 0xFFFFFFFF
@@ -43,6 +43,17 @@ def _arg(args, k, default=None):
     if isinstance(args, dict):
         return args.get(k, default)
     return getattr(args, k, default)
+
+
+def arena_precisions(args):
+    """(player 1's, player 2's) nn_precision: args' value for both, or its two entries."""
+    p = nn_precision_arg(args)
+    if isinstance(p, str):
+        return (p, p)
+    p = tuple(p)
+    if len(p) != 2:
+        raise ValueError(f"nn_precision: expected one mode or a pair, got {len(p)} values")
+    return p
 
 
 def one_vs_two(i):
@@ -60,7 +71,11 @@ class BatchedArena:
         self.seed, self.game_base = int(seed), int(game_base)
         self.check_valid = check_valid
         if evaluators is None:
-            evaluators = (evaluator_for(self.e, nnet1, self.B), evaluator_for(self.e, nnet2, self.B))
+            # args.nn_precision: one fused-kernel mode for both players, or a pair (player 1's,
+            # player 2's: one network against itself at two precisions)
+            prec = arena_precisions(args)
+            evaluators = (evaluator_for(self.e, nnet1, self.B, precision=prec[0]),
+                          evaluator_for(self.e, nnet2, self.B, precision=prec[1]))
         margs = dict(numMCTSSims=int(_arg(args, "numMCTSSims", 100)), cpuct=float(_arg(args, "cpuct", 1.0)),
                      fpu=float(_arg(args, "fpu", 0.0)), prob_fullMCTS=1.0,
                      ratio_fullMCTS=int(_arg(args, "ratio_fullMCTS", 5) or 1),

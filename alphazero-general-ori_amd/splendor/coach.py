@@ -16,7 +16,7 @@ import torch
 from .env import unpack_mask
 from .arena import BatchedArena, accept_new_network
 from .examples import ExampleHistory, ExampleSet
-from .search import evaluator_for
+from .search import evaluator_for, nn_precision_arg
 from .selfplay import SelfPlay, gather_examples
 
 
@@ -46,7 +46,8 @@ class Coach:
         B = int(batch or _arg(args, "numEps", 1))
         self.B = B
         self.seed = seed
-        self.sp = SelfPlay(game.engine, B, args, evaluator=evaluator_for(game.engine, nnet, B),
+        self.sp = SelfPlay(game.engine, B, args,
+                           evaluator=evaluator_for(game.engine, nnet, B, precision=nn_precision_arg(args)),
                            dirichlet_noise=float(_arg(args, "dirichletAlpha", 0.0)) > 0, seed=seed,
                            board_base=board_base)
         self.sp.reset()
@@ -109,7 +110,8 @@ class Coach:
     def refresh_network(self):
         """Re-pack the leaf evaluator after the network's weights changed (the fused kernel
         reads a packed copy)."""
-        self.sp.evaluator = evaluator_for(self.game.engine, self.nnet, self.B)
+        self.sp.evaluator = evaluator_for(self.game.engine, self.nnet, self.B,
+                                          precision=nn_precision_arg(self.args))
 
     def learn(self, pnet=None, log=None):
         """Coach.learn (Coach.py:102-164): for numIters iterations, numEps self-play games

@@ -10,6 +10,8 @@ terms once, the score-diff head (training-only) is skipped, and "int8 leaves -> 
 as one fused HIP kernel (csrc/nnet.hip, spl_nn_forward; fp32 MFMA) — or, for reference,
 as the PyTorch-ROCm FoldedNet, optionally captured in a HIP graph at a fixed batch.
 Returns exp(masked log_softmax(pi)) and tanh(v) like GenericNNetWrapper.predict (:141-168).
+The fused kernel's opt-in reduced-precision modes (precision="bf16x2" / "bf16", PRECISIONS;
+spl_nn_forward_mode) are defined by `reduced_forward`; the default "f32" is the exact kernel.
 """
 import ctypes as C
 
@@ -279,13 +281,75 @@ def pack_weights(folded, n_players):
     return out
 
 
+# precision modes of the fused kernel (include/splendor_amd.h, spl_nn_forward_mode): name ->
+# SPL_NN_* value; the mode multiplies the 3 - value leading bf16 parts of every operand
+PRECISIONS = {"f32": 0, "bf16x2": 1, "bf16": 2}
+
+
+def precision_mode(precision):
+    """Precision name -> SPL_NN_* value; ValueError for anything else."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"unknown nn precision {precision!r}: expected one of {sorted(PRECISIONS)}")
+    return PRECISIONS[precision]
+
+
+def _reduced_linear(x, w, b, parts):
+    """The mode's definition of F.linear(x, w, b) for f32 x, w: both operands split by
+    _bf16_parts, the products of parts (i, j) with i + j < parts summed in float64 (each is
+    exact there), the bias added, rounded to float32."""
+    xs = [(p << 16).to(torch.int32).view(torch.float32).double() for p in _bf16_parts(x)]
+    ws = [(p << 16).to(torch.int32).view(torch.float32).double() for p in _bf16_parts(w)]
+    acc = torch.zeros(x.shape[:-1] + (w.shape[0],), dtype=torch.float64, device=x.device)
+    for i in range(parts):
+        for j in range(parts - i):
+            acc = acc + xs[i] @ ws[j].t()
+    return (acc + b.double()).float()
+
+
+@torch.no_grad()
+def reduced_forward(folded, board, valid, precision):
+    """Host reference that defines the fused kernel's precision modes: FoldedNet.forward with
+    every F.linear replaced by _reduced_linear (the mode's leading bf16 parts of both operands,
+    products summed in float64, one rounding to float32 per layer output); everything between the
+    linears in float32 as in FoldedNet; the masked softmax and tanh in float64. board [B,R,7]
+    (integer-valued: exact in one part, so dense2d_1 has the weight's parts only), valid bool
+    [B,409]. Returns (pi, v) float64. "f32" is the exact kernel's six-product arithmetic."""
+    parts = 3 - precision_mode(precision)
+    f = folded
+
+    def lin(x, w, b):
+        return _reduced_linear(x.float().contiguous(), w, b, parts)
+    x = board.float().transpose(-1, -2)                                   # [B, 7, R]
+    x = F.relu(lin(x, f.w1, f.b1) * f.s1 + f.t1)
+    x = F.relu(lin(x, f.w2, f.b2))
+    d = F.relu(lin(x[..., 32:], f.wp1, f.bp1) * f.sp1 + f.tp1)
+    x = f._pool(x, 4, 8, d)
+    x = F.relu(lin(x, f.w3, f.b3))
+    x = _col_pool(x)
+    x = F.relu(lin(x, f.w4, f.b4))
+    x = f._pool(x, 4, 4, F.relu(lin(x[..., 16:], f.wp4, f.bp4)))
+    x = F.relu(lin(x, f.w5a, f.b5a))
+    x = F.relu(lin(x, f.w5b, f.b5b))
+    x = f._pool(x, 4, 4, F.relu(lin(x[..., 16:], f.wp5, f.bp5))).squeeze(1)
+    pi = lin(lin(x, f.wpi1, f.bpi1), f.wpi2, f.bpi2).double()
+    pi = torch.softmax(pi.masked_fill(~valid, -1e8), 1)
+    v = torch.tanh(lin(lin(x, f.wv1, f.bv1), f.wv2, f.bv2).double())
+    return pi, v
+
+
 class FusedNet:
     """SplendorNNet inference through the fused HIP kernel (spl_nn_forward): int8 leaf
-    boards + packed masks -> (softmax policy, tanh value), all fp32."""
+    boards + packed masks -> (softmax policy, tanh value), all fp32.
 
-    def __init__(self, net, n_players, device):
+    precision: "f32" (default: the exact kernel through spl_nn_forward / _indexed), or the opt-in
+    reduced modes "bf16x2" / "bf16" through spl_nn_forward_mode (reduced_forward defines them;
+    DESIGN.md §4). Reduced modes change search trees: data generation and the arena only."""
+
+    def __init__(self, net, n_players, device, precision="f32"):
         self.n = n_players
         self.device = torch.device(device)
+        self.precision = precision
+        self.mode = precision_mode(precision)
         self.w = pack_weights(FoldedNet(net).to(self.device).eval(), n_players)
 
     def __call__(self, leaf_state, leaf_mask, pi=None, v=None, index=None, count=None):
@@ -296,7 +360,11 @@ class FusedNet:
         pi = pi if pi is not None else torch.empty((B, ACTIONS), dtype=torch.float32, device=self.device)
         v = v if v is not None else torch.empty((B, self.n), dtype=torch.float32, device=self.device)
         s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if index is None:
+        if self.mode:
+            _lib.check(_lib.lib().spl_nn_forward_mode(self.n, B, _ptr(leaf_state), _ptr(leaf_mask), _ptr(index),
+                                                      _ptr(count), _ptr(self.w), _ptr(pi), _ptr(v), self.mode, s),
+                       "spl_nn_forward_mode")
+        elif index is None:
             _lib.check(_lib.lib().spl_nn_forward(self.n, B, _ptr(leaf_state), _ptr(leaf_mask), _ptr(self.w),
                                                  _ptr(pi), _ptr(v), s), "spl_nn_forward")
         else:
@@ -321,12 +389,17 @@ class LeafEvaluator:
 
     fused=True (default): one spl_nn_forward launch (the fused HIP network kernel).
     fused=False: the PyTorch-ROCm FoldedNet (hipBLASLt GEMMs; reference for the tests),
-    optionally captured in a HIP graph."""
+    optionally captured in a HIP graph.
+    precision: the fused kernel's mode, "f32" (default, exact), "bf16x2" or "bf16" (FusedNet);
+    the FoldedNet path has f32 only."""
 
-    def __init__(self, engine, net, B, use_graph=True, fused=True):
+    def __init__(self, engine, net, B, use_graph=True, fused=True, precision="f32"):
         self.e = engine
         self.B = B
-        self.fused = FusedNet(net, engine.n, engine.device) if fused else None
+        self.precision = precision
+        if precision_mode(precision) and not fused:
+            raise ValueError(f"precision {precision!r} needs the fused kernel (fused=True)")
+        self.fused = FusedNet(net, engine.n, engine.device, precision=precision) if fused else None
         self.net = FoldedNet(net).to(engine.device).eval()
         dev = engine.device
         if fused:

@@ -41,11 +41,22 @@ class PredictEvaluator:
         return torch.from_numpy(pi).to(dev), torch.from_numpy(v).to(dev)
 
 
-def evaluator_for(engine, nnet, batch=1):
+def nn_precision_arg(args):
+    """args.nn_precision / args['nn_precision'] (the fused kernel's precision mode, or a pair of
+    modes for BatchedArena's two players); "f32" when absent."""
+    p = args.get("nn_precision") if isinstance(args, dict) else getattr(args, "nn_precision", None)
+    return "f32" if p is None else p
+
+
+def evaluator_for(engine, nnet, batch=1, precision=None):
+    """precision: "f32" (default; None means it), "bf16x2" or "bf16" (splendor.nnet.PRECISIONS),
+    the fused kernel's mode for a device-side network; a reference-style nnet.predict has none."""
     from .NNet import NNetWrapper
-    from .nnet import LeafEvaluator
+    from .nnet import LeafEvaluator, precision_mode
+    precision = "f32" if precision is None else precision
+    precision_mode(precision)                                  # (unknown names raise here)
     if isinstance(nnet, NNetWrapper):
-        return LeafEvaluator(engine, nnet.nnet, batch, use_graph=False)
+        return LeafEvaluator(engine, nnet.nnet, batch, use_graph=False, precision=precision)
     return PredictEvaluator(engine, nnet)
 
 
@@ -55,7 +66,8 @@ class MCTS:
     def __init__(self, game, nnet, args, dirichlet_noise=False, batch_info=None):
         self.game, self.nnet, self.args = game, nnet, args
         seed = getattr(args, "seed", None) if not isinstance(args, dict) else args.get("seed")
-        self._tree = BatchedMCTS(game.engine, 1, args, evaluator_for(game.engine, nnet),
+        self._tree = BatchedMCTS(game.engine, 1, args,
+                                 evaluator_for(game.engine, nnet, precision=nn_precision_arg(args)),
                                  dirichlet_noise=dirichlet_noise, seed=seed or 0x5EED)
         self._fresh = True
         MCTS._instances.add(self)

@@ -331,6 +331,30 @@ int spl_nn_forward(int n_players, int B, const int8_t *leaf_state, const uint64_
 int spl_nn_forward_indexed(int n_players, int B, const int8_t *leaf_state, const uint64_t *leaf_mask,
                            const int32_t *leaf_index, const int32_t *leaf_count, const float *packed_weights,
                            float *pi, float *v, void *hip_stream);
+/* Opt-in reduced-precision modes of the same kernel. precision = the number P of leading bf16
+ * parts (hi, mid, lo by truncation) of every matrix-product operand that enter the MFMAs:
+ *
+ *     mode  name            P   products per chunk                     weight parts read
+ *     0     SPL_NN_F32      3   six (hh, hm, mh, hl, lh, mm)           hi, mid, lo
+ *     1     SPL_NN_BF16X2   2   hh, hm, mh                             hi, mid
+ *     2     SPL_NN_BF16     1   hh                                     hi
+ *
+ * (dense2d_1's int8 boards are exact in one part: P weight-part products there.) Truncation
+ * applies only where an operand enters an MFMA; accumulators, biases, BatchNorm affines, ReLU,
+ * pooling, the masked softmax and tanh stay f32 on each layer's untruncated outputs. The packed
+ * weights are the same in every mode; parts that are not multiplied are not read. Relative
+ * operand error: 2^-16 (BF16X2), 2^-8 (BF16). Reduced modes change search trees: they are for
+ * self-play data generation and the arena, not for parity checks.
+ * leaf_index == NULL and leaf_count == NULL: rows 0 .. B as spl_nn_forward; both non-NULL: the
+ * segmented list of spl_nn_forward_indexed; exactly one NULL, or a precision outside 0 .. 2:
+ * SPL_EINVAL before any launch. spl_nn_forward and spl_nn_forward_indexed are SPL_NN_F32. */
+#define SPL_NN_F32 0
+#define SPL_NN_BF16X2 1
+#define SPL_NN_BF16 2
+int spl_nn_forward_mode(int n_players, int B, const int8_t *leaf_state, const uint64_t *leaf_mask,
+                        const int32_t *leaf_index, const int32_t *leaf_count,
+                        const float *packed_weights, float *pi, float *v, int precision,
+                        void *hip_stream);
 
 #ifdef __cplusplus
 }
