@@ -567,6 +567,40 @@ __constant__ int8_t K_CARD_SYM[3][4] = {{1, 3, 0, 2}, {2, 0, 3, 1}, {3, 2, 1, 0}
 __constant__ int8_t K_RSV_SYM[4][2][3] = {{{-1, -1, -1}, {-1, -1, -1}}, {{-1, -1, -1}, {-1, -1, -1}},
                                           {{1, 0, 2}, {-1, -1, -1}}, {{1, 2, 0}, {2, 0, 1}}};
 
+// _nb_of_reserved_cards (:770-774) of player p: the first empty reserve slot
+template <int N>
+__device__ __forceinline__ int nb_reserved(const int8_t *s, int p) {
+    int r = 3;
+    for (int c = 2; c >= 0; c--)
+        if (sum5(HbmRows{s}(Lay<N>::RSV + 6 * p + 2 * c)) == 0) r = c;
+    return r;
+}
+// Source of state byte i / action a in the variant that permutes tier `tier`'s visible cards
+// (tier >= 0) or player p's reserved cards (p >= 0) by perm; identity: tier = p = -1.
+template <int N>
+__device__ __forceinline__ int sym_src_byte(int i, int tier, int p, const int8_t *perm) {
+    using Lx = Lay<N>;
+    const int r = i / 7, c = i - 7 * (i / 7);
+    if (tier >= 0 && r >= Lx::TIERS + 8 * tier && r < Lx::TIERS + 8 * tier + 8) {
+        const int rr = r - Lx::TIERS - 8 * tier;
+        return 7 * (Lx::TIERS + 8 * tier + 2 * perm[rr >> 1] + (rr & 1)) + c;
+    }
+    if (p >= 0 && r >= Lx::RSV + 6 * p && r < Lx::RSV + 6 * p + 6) {
+        const int rr = r - Lx::RSV - 6 * p;
+        return 7 * (Lx::RSV + 6 * p + 2 * perm[rr >> 1] + (rr & 1)) + c;
+    }
+    return i;
+}
+__device__ __forceinline__ int sym_src_action(int a, int tier, int p, const int8_t *perm) {
+    int src = a;
+    if (tier >= 0) {
+        if (a >= 4 * tier && a < 4 * tier + 4) src = 4 * tier + perm[a - 4 * tier];
+        if (a >= 12 + 4 * tier && a < 16 + 4 * tier) src = 12 + 4 * tier + perm[a - 12 - 4 * tier];
+    }
+    if (p == 0 && a >= 27 && a < 30) src = 27 + perm[a - 27];
+    return src;
+}
+
 template <int N>
 __global__ __launch_bounds__(THREADS) void k_symmetries(int E, const int8_t *__restrict__ state,
                                                         const float *__restrict__ pi,
@@ -584,11 +618,7 @@ __global__ __launch_bounds__(THREADS) void k_symmetries(int E, const int8_t *__r
     wave_copy_bytes(s, state + (size_t)e * Lx::S, Lx::S);
     int nres[N];
 #pragma unroll
-    for (int p = 0; p < N; p++) {        // _nb_of_reserved_cards (:770-774)
-        nres[p] = 3;
-        for (int c = 2; c >= 0; c--)
-            if (sum5(HbmRows{s}(Lx::RSV + 6 * p + 2 * c)) == 0) nres[p] = c;
-    }
+    for (int p = 0; p < N; p++) nres[p] = nb_reserved<N>(s, p);
     for (int k = 0; k < K; k++) {
         int tier = -1, p = -1;
         const int8_t *perm = nullptr;
@@ -601,19 +631,7 @@ __global__ __launch_bounds__(THREADS) void k_symmetries(int E, const int8_t *__r
         if (l == 0) present[(size_t)e * K + k] = 1;
         int8_t *os = ostate + ((size_t)e * K + k) * Lx::S;
         // state bytes: rows of the permuted block come from the source row pair
-        for (int i = l; i < Lx::S; i += 64) {
-            int src = i;
-            const int r = i / 7, c = i - 7 * (i / 7);
-            if (tier >= 0 && r >= Lx::TIERS + 8 * tier && r < Lx::TIERS + 8 * tier + 8) {
-                const int rr = r - Lx::TIERS - 8 * tier;
-                src = 7 * (Lx::TIERS + 8 * tier + 2 * perm[rr >> 1] + (rr & 1)) + c;
-            }
-            if (p >= 0 && r >= Lx::RSV + 6 * p && r < Lx::RSV + 6 * p + 6) {
-                const int rr = r - Lx::RSV - 6 * p;
-                src = 7 * (Lx::RSV + 6 * p + 2 * perm[rr >> 1] + (rr & 1)) + c;
-            }
-            os[i] = s[src];
-        }
+        for (int i = l; i < Lx::S; i += 64) os[i] = s[sym_src_byte<N>(i, tier, p, perm)];
         // policy and legality: action a takes the source action's entry
         const float *ip = pi + (size_t)e * SPL_ACTIONS;
         float *op = opi + ((size_t)e * K + k) * SPL_ACTIONS;
@@ -621,17 +639,122 @@ __global__ __launch_bounds__(THREADS) void k_symmetries(int E, const int8_t *__r
 #pragma unroll
         for (int ch = 0; ch < 7; ch++) {
             const int a = 64 * ch + l;
-            int src = a;
-            if (tier >= 0) {
-                if (a >= 4 * tier && a < 4 * tier + 4) src = 4 * tier + perm[a - 4 * tier];
-                if (a >= 12 + 4 * tier && a < 16 + 4 * tier) src = 12 + 4 * tier + perm[a - 12 - 4 * tier];
-            }
-            if (p == 0 && a >= 27 && a < 30) src = 27 + perm[a - 27];
+            const int src = sym_src_action(a, tier, p, perm);
             if (a < SPL_ACTIONS) op[a] = ip[src];
             const bool bit = a < SPL_ACTIONS && ((iv[src >> 6] >> (src & 63)) & 1);
             const uint64_t word = __ballot(bit);
             if (l == 0) ovalid[((size_t)e * K + k) * 7 + ch] = word;
         }
+    }
+}
+
+// Variants Board.get_symmetries emits for a board: 10 + sum over players of
+// (0, 0, 1, 2)[#reserved]. ~30 bytes read per board: one lane per board straight from HBM.
+template <int N>
+__global__ __launch_bounds__(256) void k_symmetry_counts(int E, const int8_t *__restrict__ state,
+                                                         uint8_t *__restrict__ count) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int8_t *s = state + (size_t)e * Lay<N>::S;
+    int k = 10;
+#pragma unroll
+    for (int p = 0; p < N; p++) {
+        const int nr = nb_reserved<N>(s, p);
+        k += nr >= 2 ? nr - 1 : 0;
+    }
+    count[e] = (uint8_t)k;
+}
+
+// Training rows from unexpanded examples, one wave per output row: row i is variant number
+// ordinal[i] (among the variants k_symmetries marks present, in its order) of example
+// example[i], written as the network's input (board cast to f32), the permuted policy, the
+// permuted legality as one byte per action, and the example's winner / scdiff. The source
+// board is staged in the wave's LDS slot; #reserved is read only for the players the
+// ordinal walks over. A row whose example or ordinal is out of range reads nothing, is
+// written as zeros and ORs SPL_ERR_BAD_INDEX into *err.
+template <int N>
+__global__ __launch_bounds__(THREADS) void k_gather_examples(
+    int E, int M, const int8_t *__restrict__ state, const float *__restrict__ pi,
+    const uint64_t *__restrict__ valid, const float *__restrict__ winner,
+    const int32_t *__restrict__ scdiff, const int64_t *__restrict__ example,
+    const int32_t *__restrict__ ordinal, float *__restrict__ x, float *__restrict__ opi,
+    uint8_t *__restrict__ ovalid, float *__restrict__ owinner, int32_t *__restrict__ oscdiff,
+    int32_t *err) {
+    using Lx = Lay<N>;
+    __shared__ __align__(16) int8_t lds[WAVES][(Lx::S + 15) & ~15];   // raw 7-byte rows
+    const int w = threadIdx.x >> 6, i = blockIdx.x * WAVES + w;
+    if (i >= M) return;
+    const int l = lane_id();
+    const int64_t e = (int64_t)uniform64((uint64_t)example[i]);
+    const int k = uniform(ordinal[i]);
+    int8_t *s = lds[w];
+    float *ox = x + (size_t)i * Lx::S;
+    float *op = opi + (size_t)i * SPL_ACTIONS;
+    uint8_t *ov = ovalid + (size_t)i * SPL_ACTIONS;
+    // dword stores of the 409 legality bytes: `head` bytes up to the first aligned address,
+    // nd dwords, then the tail (rows are 409 bytes, so the alignment differs row to row)
+    const int head = (int)((4 - ((uintptr_t)ov & 3)) & 3);
+    const int nd = (SPL_ACTIONS - head) >> 2, tail = head + 4 * nd;
+
+    bool ok = e >= 0 && e < E && k >= 0;
+    int tier = -1, p = -1;
+    const int8_t *perm = K_CARD_SYM[0];
+    if (ok) {
+        wave_copy_bytes(s, state + (size_t)e * Lx::S, Lx::S);
+        __builtin_amdgcn_wave_barrier();
+        if (k >= 1 && k <= 9) {
+            tier = (k - 1) / 3;
+            perm = K_CARD_SYM[(k - 1) % 3];
+        } else if (k >= 10) {            // the (k-10)-th defined reserve permutation, players in order
+            int rem = k - 10;
+            ok = false;
+            for (int q = 0; q < N && !ok; q++) {
+                const int nr = uniform(nb_reserved<N>(s, q));
+                const int c = nr >= 2 ? nr - 1 : 0;
+                if (rem < c) {
+                    p = q;
+                    perm = K_RSV_SYM[nr][rem];
+                    ok = true;
+                }
+                rem -= c;
+            }
+        }
+    }
+    if (!ok) {
+        for (int j = l; j < Lx::S; j += 64) ox[j] = 0.f;
+        for (int a = l; a < SPL_ACTIONS; a += 64) op[a] = 0.f;
+        if (l < head) ov[l] = 0;
+        for (int d = l; d < nd; d += 64) *reinterpret_cast<uint32_t *>(ov + head + 4 * d) = 0u;
+        if (tail + l < SPL_ACTIONS) ov[tail + l] = 0;
+        if (l < N) {
+            owinner[(size_t)i * N + l] = 0.f;
+            oscdiff[(size_t)i * N + l] = 0;
+        }
+        if (err && l == 0) atomicOr(err, SPL_ERR_BAD_INDEX);
+        return;
+    }
+    for (int j = l; j < Lx::S; j += 64) ox[j] = (float)s[sym_src_byte<N>(j, tier, p, perm)];
+    const float *ip = pi + (size_t)e * SPL_ACTIONS;
+    for (int a = l; a < SPL_ACTIONS; a += 64) op[a] = ip[sym_src_action(a, tier, p, perm)];
+    // the 7 mask words are wave-uniform (scalar loads); a lane picks its word by selects, so
+    // they stay in registers (an indexed array would be spilled to LDS or scratch)
+    const uint64_t *iv = valid + (size_t)e * SPL_MASK_WORDS;
+    const uint64_t v0 = iv[0], v1 = iv[1], v2 = iv[2], v3 = iv[3], v4 = iv[4], v5 = iv[5], v6 = iv[6];
+    auto legal = [=](int a) -> uint32_t {
+        const int src = sym_src_action(a, tier, p, perm), c = src >> 6;
+        const uint64_t word = c == 0 ? v0 : c == 1 ? v1 : c == 2 ? v2 : c == 3 ? v3 : c == 4 ? v4 : c == 5 ? v5 : v6;
+        return (uint32_t)(word >> (src & 63)) & 1u;
+    };
+    if (l < head) ov[l] = (uint8_t)legal(l);
+    for (int d = l; d < nd; d += 64) {
+        const int a = head + 4 * d;
+        *reinterpret_cast<uint32_t *>(ov + a) =
+            legal(a) | legal(a + 1) << 8 | legal(a + 2) << 16 | legal(a + 3) << 24;
+    }
+    if (tail + l < SPL_ACTIONS) ov[tail + l] = (uint8_t)legal(tail + l);
+    if (l < N) {
+        owinner[(size_t)i * N + l] = winner[(size_t)e * N + l];
+        oscdiff[(size_t)i * N + l] = scdiff[(size_t)e * N + l];
     }
 }
 
@@ -761,6 +884,31 @@ int spl_symmetries(const spl_ctx *c, int E, const int8_t *state, const float *pi
     SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_symmetries<N>, wave_grid(E), dim3(THREADS), 0,
                                           (hipStream_t)hs, E, state, pi, valid, out_state, out_pi,
                                           out_valid, present));
+    return check_launch();
+}
+
+int spl_symmetry_counts(const spl_ctx *c, int E, const int8_t *state, uint8_t *count, void *hs) {
+    if (!ok_ctx(c) || E < 0 || (E && (!state || !count))) return SPL_EINVAL;
+    if (!E) return 0;
+    SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_symmetry_counts<N>, lane_grid(E), dim3(256), 0,
+                                          (hipStream_t)hs, E, state, count));
+    return check_launch();
+}
+
+int spl_gather_examples(const spl_ctx *c, int E, int M, const int8_t *state, const float *pi,
+                        const uint64_t *valid, const float *winner, const int32_t *scdiff,
+                        const int64_t *example, const int32_t *ordinal, float *x, float *out_pi,
+                        uint8_t *out_valid, float *out_winner, int32_t *out_scdiff, int32_t *err,
+                        void *hs) {
+    if (!ok_ctx(c) || E < 0 || M < 0 ||
+        (E && M && (!state || !pi || !valid || !winner || !scdiff || !example || !ordinal || !x ||
+                    !out_pi || !out_valid || !out_winner || !out_scdiff)))
+        return SPL_EINVAL;
+    if (!E || !M) return 0;
+    SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_gather_examples<N>, wave_grid(M), dim3(THREADS), 0,
+                                          (hipStream_t)hs, E, M, state, pi, valid, winner, scdiff,
+                                          example, ordinal, x, out_pi, out_valid, out_winner,
+                                          out_scdiff, err));
     return check_launch();
 }
 

@@ -18,11 +18,12 @@ import torch
 import torch.optim as optim
 
 from .env import unpack_mask
-from .examples import ExampleSet
+from .examples import ExampleSet, LazySymmetryExamples
 from .nnet import SplendorNNet, remap_policy_head
 
 DEFAULT_NN_ARGS = dict(learn_rate=0.0003, dropout=0.3, epochs=2, batch_size=32, vl_weight=10.0,
-                       surprise_weight=False)          # main.py:24-33, 121-127
+                       surprise_weight=False,          # main.py:24-33, 121-127
+                       symmetry_sampling="all")        # lazy example sets only, see train
 
 
 # ---------------------------------------------------------------- losses (:171-183)
@@ -183,11 +184,25 @@ class NNetWrapper:
         return (loss_pi(pis, out_pi), loss_v(vs, out_v), loss_scdiff_cdf(t_sd, out_sd),
                 loss_scdiff_pdf(t_sd, out_sd))
 
-    def train(self, examples, generator=None, sample_ids=None, shared=None):
+    def train(self, examples, generator=None, sample_ids=None, shared=None, sample_variants=None):
         """One GenericNNetWrapper.train call over `examples` (ExampleSet, or the reference's
         list of tuples): epochs x (len // batch_size) Adam steps on batches sampled without
         replacement, total loss l_pi + vl_weight * l_v + l_cdf + l_pdf, OneCycleLR stepped
         per batch. Returns the mean of each loss over the last epoch.
+
+        `examples` may also be a LazySymmetryExamples (stored positions, variants produced
+        when a batch is assembled). With nn_args["symmetry_sampling"] = "all" (default) its
+        row space is every present variant in expand_symmetries' order, so ids, sample_ids
+        and the step count mean what they mean for the materialised set and every step
+        feeds the network the same tensor values; only the batch assembly differs (one
+        gather kernel instead of five index_selects, a cast and the mask unpacking).
+        "one" is NOT the reference's sampling: the row space is the stored positions
+        (len = n_base), and each time a position is picked one of its present variants is
+        drawn uniformly (ordinal = floor(u * count), u from torch.rand(batch_size) on the
+        batch generator right after the permutation), so an epoch is n_base // batch_size
+        steps over positions instead of len // batch_size steps over variants. sample_variants injects those ordinals (one int array
+        of batch_size per step) as sample_ids injects the rows. A materialised ExampleSet
+        ignores the setting.
 
         sample_ids: the batches themselves (one index array of batch_size per step, epochs x
         batch_count of them) — the reference's np.random.choice draws (:70) injected, as the
@@ -207,17 +222,25 @@ class NNetWrapper:
         minimum over ranks, so no rank waits in an all-reduce the others never enter.
         shared: None detects it (example count and content checksum agree on every rank);
         True / False force a path (every rank must pass the same)."""
-        if not isinstance(examples, ExampleSet):
+        lazy = isinstance(examples, LazySymmetryExamples)
+        if not lazy and not isinstance(examples, ExampleSet):
             examples = ExampleSet.from_tuples(list(examples))
         if self.args["surprise_weight"]:
             # the reference's weights are [E, n] (one per player) and np.random.choice
             # rejects a 2-D p, so surprise weighting cannot run there either
             raise ValueError("surprise_weight: per-example surprise is a vector (reference raises)")
+        sampling = self.args.get("symmetry_sampling", "all")
+        if sampling not in ("all", "one"):
+            raise ValueError(f"symmetry_sampling: 'all' or 'one', not {sampling!r}")
+        one = lazy and sampling == "one"     # a materialised set has no variants left to draw
+        if sample_variants is not None and not one:
+            raise ValueError("sample_variants: only with lazy examples and symmetry_sampling='one'")
         ex = examples.to(self.device)
-        E, bs, epochs = len(ex), int(self.args["batch_size"]), int(self.args["epochs"])
+        cols = ex.base if lazy else ex       # the stored columns (checksum, shared / different sets)
+        E, bs, epochs = (ex.n_base if one else len(ex)), int(self.args["batch_size"]), int(self.args["epochs"])
         dist, rank, world = _dist_world()
         if shared is None:
-            shared = _same_everywhere(ex, self.device)
+            shared = _same_everywhere(cols, self.device)
         self.last_shared = bool(shared)
         batch_count = _agreed_batch_count(E // bs, self.device)
         if batch_count == 0:
@@ -226,12 +249,18 @@ class NNetWrapper:
             sample_ids = [torch.as_tensor(np.asarray(i, dtype=np.int64), device=self.device) for i in sample_ids]
             if len(sample_ids) != epochs * batch_count or any(len(i) != bs for i in sample_ids):
                 raise ValueError(f"sample_ids: need {epochs * batch_count} batches of {bs}")
+        if sample_variants is not None:
+            sample_variants = [torch.as_tensor(np.asarray(i, dtype=np.int32), device=self.device)
+                               for i in sample_variants]
+            if len(sample_variants) != epochs * batch_count or any(len(i) != bs for i in sample_variants):
+                raise ValueError(f"sample_variants: need {epochs * batch_count} batches of {bs}")
         params = list(self.nnet.parameters())
         if self.optimizer is None:
             self.optimizer = optim.Adam(params, lr=self.args["learn_rate"])
         scheduler = optim.lr_scheduler.OneCycleLR(self.optimizer, max_lr=self.args["learn_rate"],
                                                   steps_per_epoch=batch_count, epochs=epochs)
-        gen = None if sample_ids is not None else (generator or _batch_generator(self.device))
+        draws = sample_ids is None or (one and sample_variants is None)
+        gen = (generator or _batch_generator(self.device)) if draws else None
         if gen is not None and not shared and world > 1:    # different sets: decorrelate the ranks
             s0 = int(torch.randint(0, 2 ** 62, (1,), generator=gen, device=gen.device).item())
             gen = torch.Generator(device=self.device)
@@ -245,9 +274,18 @@ class NNetWrapper:
                     ids = sample_ids[step]
                 else:
                     ids = torch.randperm(E, generator=gen, device=self.device)[:bs]
+                ords = None
+                if one:      # one present variant of each picked position, uniformly
+                    if sample_variants is not None:
+                        ords = sample_variants[step]
+                    else:
+                        u = torch.rand(bs, generator=gen, device=self.device).double()   # u < 1: exact floor
+                        cnt = ex.counts.index_select(0, ids).double()
+                        ords = torch.minimum((u * cnt).floor(), cnt - 1).to(torch.int32)
                 weight = None
                 if shared and world > 1:
                     ids = ids[rank::world]
+                    ords = ords[rank::world] if one else None
                     weight = len(ids) / bs       # this slice's share of the global batch
                 step += 1
                 self.optimizer.zero_grad(set_to_none=True)
@@ -256,11 +294,14 @@ class NNetWrapper:
                     self.optimizer.step()
                     scheduler.step()
                     continue
-                boards = ex.board.index_select(0, ids).float()
-                valids = unpack_mask(ex.valids.index_select(0, ids))
-                pis = ex.pi.index_select(0, ids)
-                vs = ex.winner.index_select(0, ids)
-                sds = ex.scdiff.index_select(0, ids)
+                if lazy:     # one gather kernel launch: variant, cast and mask unpacking included
+                    boards, pis, vs, sds, valids = ex.batch_pairs(ids, ords) if one else ex.batch(ids)
+                else:
+                    boards = ex.board.index_select(0, ids).float()
+                    valids = unpack_mask(ex.valids.index_select(0, ids))
+                    pis = ex.pi.index_select(0, ids)
+                    vs = ex.winner.index_select(0, ids)
+                    sds = ex.scdiff.index_select(0, ids)
                 l_pi, l_v, l_c, l_p = self.losses(boards, pis, vs, sds, valids)
                 total = l_pi + self.args["vl_weight"] * l_v + l_c + l_p
                 total.backward()
@@ -271,6 +312,8 @@ class NNetWrapper:
                 if self._loss_log is not None:
                     self._loss_log.append([float(x.detach()) for x in (l_pi, l_v, l_c, l_p)])
             means = (acc / batch_count).tolist()
+            if lazy:
+                ex.check_errors()        # an injected row or variant out of range (flag set on device)
         self.nnet.eval()
         return {"pi": means[0], "v": means[1], "scdiff": means[2]}
 

@@ -12,7 +12,8 @@ LIB_PATH = os.environ.get("SPLENDOR_AMD_LIB") or os.path.join(PKG_ROOT, "libsple
 
 ABI_VERSION = 11
 EINVAL, EDEVICE = -1, -2
-BACKUP_DEFER_GC = 4                 # spl_mcts_backup_kind: SPL_BACKUP_DEFER_GC
+ERR_BAD_ACTION, ERR_BAD_INDEX = 1, 2   # bits OR-ed into a call's device `err` word
+BACKUP_DEFER_GC = 4              # spl_mcts_backup_kind: SPL_BACKUP_DEFER_GC
 
 
 class NativeEngineMissing(RuntimeError):
@@ -32,6 +33,8 @@ _SIGS = {
     "spl_ctx_destroy": ([C.c_void_p], C.c_int),
     "spl_ctx_set_token_limit": ([C.c_void_p, C.c_int], C.c_int),
     "spl_symmetries": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "spl_symmetry_counts": ([C.c_void_p, C.c_int, _vp, _vp, _vp], C.c_int),
+    "spl_gather_examples": ([C.c_void_p, C.c_int, C.c_int] + [_vp] * 14, C.c_int),
     "spl_state_rows": ([C.c_void_p], C.c_int),
     "spl_state_bytes": ([C.c_void_p], C.c_int),
     "spl_init": ([C.c_void_p, C.c_int, _vp, _vp, _vp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32,

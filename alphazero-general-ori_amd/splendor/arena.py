@@ -63,7 +63,7 @@ def one_vs_two(i):
 
 class BatchedArena:
     def __init__(self, game, nnet1, nnet2, args, batch=None, seed=0x5EED, game_base=0,
-                 evaluators=None, check_valid=True):
+                 evaluators=None, check_valid=True, mem_budget=None):
         self.game, self.args = game, args
         self.e = game.engine
         self.n = self.e.n
@@ -82,9 +82,12 @@ class BatchedArena:
                      forced_playouts=bool(_arg(args, "forced_playouts", False)), dirichletAlpha=0.0,
                      temperature=list(_arg(args, "temperature", [1.25, 0.8])),
                      tempThreshold=int(_arg(args, "tempThreshold", 10)))
-        # the two players' arenas share what is free now (each would otherwise plan 80 % of it)
+        # the two players' arenas share what is free now (each would otherwise plan 80 % of it),
+        # or the caller's mem_budget bytes
         budget = None
-        if self.e.device.type == "cuda":
+        if mem_budget:
+            budget = int(mem_budget) // 2
+        elif self.e.device.type == "cuda":
             budget = int(0.4 * torch.cuda.mem_get_info(self.e.device)[0])
         self.mcts = [BatchedMCTS(self.e, self.B, margs, evaluators[k], dirichlet_noise=False,
                                  seed=self.mcts_seed(k), board_base=self.game_base, mem_budget=budget)

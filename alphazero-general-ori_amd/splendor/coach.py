@@ -6,7 +6,9 @@ recorded position with getSymmetries (Coach.py:77-80, device kernel spl_symmetri
 returns the reference's example records (board, pi, winner, scdiff, valids, surprise)
 (Coach.py:91-98). `executeEpisode()` is the one-game form. `executeIteration(k)` returns
 the same examples as a columnar `ExampleSet` and appends it to `trainExamplesHistory`
-(an `ExampleHistory`, saved as .npz by `saveTrainExamples`, Coach.py:167-190). `learn()`
+(an `ExampleHistory`, saved as .npz by `saveTrainExamples`, Coach.py:167-190); with
+`args.lazy_symmetries` it keeps the positions unexpanded (`LazySymmetryExamples`) and the
+variants are produced when training batches are assembled. `learn()`
 is Coach.learn (Coach.py:102-164): self-play iterations, training on the example history,
 the new-vs-previous BatchedArena gate and checkpoints.
 """
@@ -15,7 +17,7 @@ import torch
 
 from .env import unpack_mask
 from .arena import BatchedArena, accept_new_network
-from .examples import ExampleHistory, ExampleSet
+from .examples import ExampleHistory, ExampleSet, LazySymmetryExamples
 from .search import evaluator_for, nn_precision_arg
 from .selfplay import SelfPlay, gather_examples
 
@@ -41,15 +43,18 @@ def expand_symmetries(engine, ex):
 
 
 class Coach:
-    def __init__(self, game, nnet, args, batch=None, seed=0x5EED, board_base=0):
+    def __init__(self, game, nnet, args, batch=None, seed=0x5EED, board_base=0, mem_budget=None):
+        """mem_budget: bytes of HBM the self-play search arena may plan (default: most of
+        what is free, BatchedMCTS._plan); learn() gives its arena gate the same bound."""
         self.game, self.nnet, self.args = game, nnet, args
         B = int(batch or _arg(args, "numEps", 1))
         self.B = B
         self.seed = seed
+        self.mem_budget = mem_budget
         self.sp = SelfPlay(game.engine, B, args,
                            evaluator=evaluator_for(game.engine, nnet, B, precision=nn_precision_arg(args)),
                            dirichlet_noise=float(_arg(args, "dirichletAlpha", 0.0)) > 0, seed=seed,
-                           board_base=board_base)
+                           board_base=board_base, mem_budget=mem_budget)
         self.sp.reset()
         self.trainExamplesHistory = ExampleHistory(_arg(args, "numItersHistory"))
 
@@ -91,10 +96,16 @@ class Coach:
 
     def executeIteration(self, num_games, with_symmetries=True, gather=False):
         """Self-play examples of one iteration (Coach.learn's executeEpisode loop,
-        Coach.py:123-132) as an ExampleSet, appended to trainExamplesHistory."""
-        ex = self.executeEpisodes(num_games, with_symmetries=with_symmetries, as_tuples=False,
+        Coach.py:123-132) as an ExampleSet, appended to trainExamplesHistory. With
+        args.lazy_symmetries the recorded positions are kept unexpanded (gathered across
+        ranks as before) and a LazySymmetryExamples over them is appended instead: the same
+        rows, produced when a training batch is assembled, 10-18x less memory and disk."""
+        lazy = with_symmetries and bool(_arg(self.args, "lazy_symmetries", False))
+        ex = self.executeEpisodes(num_games, with_symmetries=with_symmetries and not lazy, as_tuples=False,
                                   gather=gather)
         exset = ExampleSet.from_drain(ex)
+        if lazy:
+            exset = LazySymmetryExamples(exset, self.game.engine)
         self.trainExamplesHistory.append(exset)
         return exset
 
@@ -103,9 +114,11 @@ class Coach:
         return self.trainExamplesHistory.save(folder or _arg(self.args, "checkpoint", "checkpoint"))
 
     def loadTrainExamples(self, folder):
-        """Coach.loadTrainExamples (:175-190): read checkpoint.examples.npz."""
+        """Coach.loadTrainExamples (:175-190): read checkpoint.examples.npz (either kind: a
+        file of unexpanded positions comes back as lazy sets on this coach's engine)."""
         self.trainExamplesHistory = ExampleHistory.load(folder, _arg(self.args, "numItersHistory"),
-                                                        device=self.game.engine.device)
+                                                        device=self.game.engine.device,
+                                                        engine=self.game.engine)
 
     def refresh_network(self):
         """Re-pack the leaf evaluator after the network's weights changed (the fused kernel
@@ -137,7 +150,7 @@ class Coach:
             self.nnet.train(self.trainExamplesHistory.merged())
             games = int(_arg(self.args, "arenaCompare", 2))
             arena = BatchedArena(self.game, self.nnet, pnet, self.args, batch=min(games, self.B),
-                                 seed=self.seed + i)
+                                 seed=self.seed + i, mem_budget=self.mem_budget)
             nwins, pwins, draws = arena.playGames(games)
             ok = accept_new_network(nwins, pwins, float(_arg(self.args, "updateThreshold", 0.55)))
             if ok:

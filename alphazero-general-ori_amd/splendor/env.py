@@ -156,6 +156,54 @@ class SplendorEngine:
                                          _ptr(os_), _ptr(op), _ptr(ov), _ptr(pr), self._s()), "spl_symmetries")
         return os_, op, ov, pr
 
+    def symmetry_counts(self, state):
+        """Number of variants Board.get_symmetries emits for each of E boards -> uint8 [E]."""
+        E = state.shape[0]
+        out = torch.empty((E,), dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.spl_symmetry_counts(self.ctx, E, _ptr(state.contiguous()), _ptr(out), self._s()),
+                   "spl_symmetry_counts")
+        return out
+
+    def check_example_columns(self, state, pi, valid, winner, scdiff):
+        """Raise unless the five example columns are what spl_gather_examples reads: contiguous
+        device tensors of the ABI's types, one row per example."""
+        E, n = state.shape[0], self.n
+        for t, dt, shape in ((state, torch.int8, (E, self.rows, 7)), (pi, torch.float32, (E, ACTIONS)),
+                             (valid, torch.int64, (E, MASK_WORDS)), (winner, torch.float32, (E, n)),
+                             (scdiff, torch.int32, (E, n))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"example column: need a contiguous device {dt} tensor of shape {shape}")
+
+    def gather_examples(self, state, pi, valid, winner, scdiff, example, ordinal, err=None, rows=None,
+                        check=True):
+        """Training rows from unexpanded example columns in one launch: row i is variant
+        number ordinal[i] (int32, among the variants get_symmetries emits, in its order) of
+        example example[i] (int64). -> (x f32 [M,R,7], pi f32 [M,409], valid bool [M,409],
+        winner f32 [M,n], scdiff int32 [M,n]). Nothing is allocated or synchronised beyond
+        the outputs; rows with an index out of range come back as zeros and set
+        _lib.ERR_BAD_INDEX in `err` (device int32, optional). `rows` (default: all of
+        `state`) is the number of examples E; check=False skips check_example_columns for
+        columns the caller has checked already."""
+        E = int(state.shape[0] if rows is None else rows)
+        M, dev, n = int(example.shape[0]), self.device, self.n
+        if check:
+            self.check_example_columns(state, pi, valid, winner, scdiff)
+        if example.dtype != torch.int64 or ordinal.dtype != torch.int32 or not example.is_cuda or \
+                not ordinal.is_cuda or not example.is_contiguous() or not ordinal.is_contiguous():
+            raise ValueError("gather_examples: example int64 / ordinal int32 contiguous device tensors")
+        if example.shape != (M,) or ordinal.shape != (M,) or E > state.shape[0] or (M and not E):
+            raise ValueError("gather_examples: example / ordinal / column sizes disagree")
+        x = torch.empty((M, self.rows, 7), dtype=torch.float32, device=dev)
+        op = torch.empty((M, ACTIONS), dtype=torch.float32, device=dev)
+        ov = torch.empty((M, ACTIONS), dtype=torch.bool, device=dev)
+        ow = torch.empty((M, n), dtype=torch.float32, device=dev)
+        osd = torch.empty((M, n), dtype=torch.int32, device=dev)
+        _lib.check(self.L.spl_gather_examples(self.ctx, E, M, _ptr(state), _ptr(pi), _ptr(valid), _ptr(winner),
+                                              _ptr(scdiff), _ptr(example), _ptr(ordinal), _ptr(x), _ptr(op),
+                                              _ptr(ov), _ptr(ow), _ptr(osd), _ptr(err), self._s()),
+                   "spl_gather_examples")
+        return x, op, ov, ow, osd
+
     def rollout_step(self, state, player, mask_out, action_out, ended_out, games_done, seed, step,
                      board_base=0):
         _lib.check(self.L.spl_rollout_step(self.ctx, state.shape[0], _ptr(state), _ptr(player),

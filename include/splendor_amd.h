@@ -38,6 +38,7 @@ extern "C" {
 #define SPL_EINVAL (-1)
 #define SPL_EDEVICE (-2)
 #define SPL_ERR_BAD_ACTION 1
+#define SPL_ERR_BAD_INDEX 2
 
 typedef struct spl_ctx spl_ctx;
 
@@ -100,6 +101,30 @@ int spl_tree_step(const spl_ctx *ctx, int B, const int8_t *parent, const int16_t
 int spl_symmetries(const spl_ctx *ctx, int E, const int8_t *state, const float *pi,
                    const uint64_t *valid, int8_t *out_state, float *out_pi, uint64_t *out_valid,
                    uint8_t *present, void *hip_stream);
+
+/* Lazy symmetry expansion: the variants are never stored; training rows are produced from
+ * the unexpanded examples when a batch is assembled.
+ * spl_symmetry_counts: number of variants Board.get_symmetries emits for each of E boards:
+ * 10 + sum over players of (0, 0, 1, 2)[#reserved cards] (SplendorLogicNumba.py:349-395).
+ * count: E u8. */
+int spl_symmetry_counts(const spl_ctx *ctx, int E, const int8_t *state, uint8_t *count,
+                        void *hip_stream);
+
+/* M training rows assembled from E unexpanded examples in one launch. Row i is variant number
+ * ordinal[i] (0-based, among the variants get_symmetries emits for that board, in its order:
+ * the present slots of spl_symmetries) of example example[i]:
+ *   x       M x R x 7 f32   the permuted board, cast (what train feeds the network)
+ *   pi      M x 409  f32    permuted policy
+ *   valid   M x 409  u8     permuted legality, one byte per action (0/1)
+ *   winner  M x n    f32,  scdiff  M x n  i32    copied from the example
+ * example: M i64, ordinal: M i32 (device). A row with example[i] outside [0, E) or
+ * ordinal[i] outside [0, count) reads nothing, is written as zeros and ORs
+ * SPL_ERR_BAD_INDEX into *err (nullable). E == 0 or M == 0 launches nothing. */
+int spl_gather_examples(const spl_ctx *ctx, int E, int M, const int8_t *state, const float *pi,
+                        const uint64_t *valid, const float *winner, const int32_t *scdiff,
+                        const int64_t *example, const int32_t *ordinal, float *x, float *out_pi,
+                        uint8_t *out_valid, float *out_winner, int32_t *out_scdiff, int32_t *err,
+                        void *hip_stream);
 
 /* One fused random-policy self-play step per board (BASELINE config 2; the move loop of
  * Coach.executeEpisode, Coach.py:71-100, with a uniform random policy):
