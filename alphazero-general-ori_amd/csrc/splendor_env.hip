@@ -34,6 +34,7 @@ __shared__ uint64_t spl_probe_last;
 __device__ uint64_t *g_rollout_timing;
 #endif
 #include "splendor_device.h"
+#include "mcts_device.h"   // ST_PLAYER
 
 using namespace spl;
 
@@ -171,6 +172,98 @@ __global__ __launch_bounds__(THREADS) void k_tree_step(int B, const int8_t *__re
         if (nxt) wave_roll_players<N>(s, s, nxt);
     }
     wave_store_board<N>(child + (size_t)b * Lx::S, s);
+}
+
+// The rule-based players (splendor_amd.h spl_player_move): one move of a random, greedy or
+// arg-max-policy player on each canonical board, wave per board. The candidate set is built
+// as a packed mask from the legality mask; one keyed draw picks among its bits.
+// Greedy lookahead: only buys (0-11 visible, 27-29 reserved) change a score and a score
+// never falls, so every other legal move scores s0 and at most 15 moves are tried, each by
+// the engine's make_move (deterministic) on a scratch copy in the wave's second LDS slot.
+template <int N>
+__global__ __launch_bounds__(THREADS) void k_player_move(int B, const int8_t *__restrict__ state,
+                                                         const uint8_t *__restrict__ active, int kind,
+                                                         const float *__restrict__ pi, int lim,
+                                                         uint64_t seed, uint32_t stream, uint32_t bbase,
+                                                         int16_t *__restrict__ action,
+                                                         uint64_t *__restrict__ cand_out,
+                                                         int32_t *__restrict__ best_out) {
+    using Lx = Lay<N>;
+    __shared__ __align__(16) int8_t lds[WAVES][2][Lx::LS];
+    const int w = threadIdx.x >> 6, b = blockIdx.x * WAVES + w;
+    if (b >= B) return;
+    if (active && !active[b]) return;
+    const int l = lane_id();
+    int8_t *s = lds[w][0], *t = lds[w][1];
+    wave_load_board<N>(s, state + (size_t)b * Lx::S);
+    uint64_t v[7], c[7];
+    wave_valid_moves<N>(s, 0, lim, v);
+#pragma unroll
+    for (int k = 0; k < 7; k++) c[k] = v[k];
+    const int s0 = get_score<N>(s, 0);
+    int best = s0;
+    if (kind == SPL_PLAYER_GREEDY) {
+        uint64_t top = 0;
+        for (uint64_t r = uniform64(v[0] & 0x38000FFFull); r; r &= r - 1) {
+            const int a = __ffsll((unsigned long long)r) - 1;
+            wave_copy_lds_board<N>(t, s);
+            Chance ch{nullptr, 0, 0, 0, 0};
+            make_move<N>(t, a, 0, true, ch);
+            __builtin_amdgcn_wave_barrier();
+            const int sa = get_score<N>(t, 0);
+            __builtin_amdgcn_wave_barrier();
+            if (sa > best) {
+                best = sa;
+                top = 0;
+            }
+            if (sa == best) top |= 1ull << a;
+        }
+        const uint64_t vis = v[0] & 0xFFFull, gems = v[0] & 0x0FFFFFFFC0000000ull;   // [0,12), [30,60)
+        const uint64_t first = best > s0 ? top : (vis ? vis : gems);
+        if (first) {
+            c[0] = first;
+#pragma unroll
+            for (int k = 1; k < 7; k++) c[k] = 0;
+        }
+    } else if (kind == SPL_PLAYER_POLICY) {
+        const float *p = pi + (size_t)b * SPL_ACTIONS;
+        float x[7], mx = 0.f;
+        bool have = false;
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const bool on = (v[k] >> l) & 1;                 // (bits >= 409 are never set)
+            x[k] = on ? p[64 * k + l] : 0.f;
+            if (on) mx = have ? fmaxf(mx, x[k]) : x[k];
+            have |= on;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ox = __shfl_xor(mx, o, 64);
+            const bool oh = __shfl_xor((int)have, o, 64);
+            if (oh) mx = have ? fmaxf(mx, ox) : ox;
+            have |= oh;
+        }
+        uint64_t any = 0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            c[k] = __ballot(((v[k] >> l) & 1) && x[k] == mx);
+            any |= c[k];
+        }
+        if (!any) {                                          // (every legal entry NaN)
+#pragma unroll
+            for (int k = 0; k < 7; k++) c[k] = v[k];
+        }
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) cnt += __popcll(c[k]);
+    const double u = philox_u01(seed, bbase + (uint32_t)b, ST_PLAYER | stream, 0);
+    const int a = select_bit(c, min((int)(u * (double)cnt), cnt - 1));
+    if (l == 0) {
+        action[b] = (int16_t)a;
+        if (best_out) best_out[b] = best;
+    }
+    if (cand_out) store_mask(cand_out + (size_t)b * 7, c);
 }
 
 // Fused random-policy self-play (splendor_amd.h spl_rollout_step / spl_rollout_run).
@@ -865,6 +958,19 @@ int spl_tree_step(const spl_ctx *c, int B, const int8_t *parent, const int16_t *
     if (!B) return 0;
     SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_tree_step<N>, wave_grid(B), dim3(THREADS), 0,
                                           (hipStream_t)hs, B, parent, action, child, err));
+    return check_launch();
+}
+
+int spl_player_move(const spl_ctx *c, int B, const int8_t *state, const uint8_t *active, int kind,
+                    const float *pi, uint64_t seed, uint32_t stream, uint32_t board_base,
+                    int16_t *action, uint64_t *cand_out, int32_t *best_out, void *hs) {
+    if (!ok_ctx(c) || !state || !action || B < 0 || kind < SPL_PLAYER_RANDOM || kind > SPL_PLAYER_POLICY ||
+        (kind == SPL_PLAYER_POLICY && !pi) || stream > 0xFFFFFFu)
+        return SPL_EINVAL;
+    if (!B) return 0;
+    SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_player_move<N>, wave_grid(B), dim3(THREADS), 0,
+                                          (hipStream_t)hs, B, state, active, kind, pi, c->token_limit,
+                                          seed, stream, board_base, action, cand_out, best_out));
     return check_launch();
 }
 

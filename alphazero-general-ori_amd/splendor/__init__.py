@@ -4,4 +4,6 @@ Modules:
   _lib          ctypes binding of libsplendor_amd.so (fails loudly if missing)
   env           batched device-resident environment (SplendorEngine, RolloutBatch)
   SplendorGame  the reference's Game interface (SplendorGame.py:11-86), engine-backed
+  SplendorPlayers  RandomPlayer / GreedyPlayer for the sequential Arena (one-board kernel calls)
+  arena, pit    BatchedArena (the Coach's gate) and BatchedPit (any two player kinds), on device
 """

@@ -14,6 +14,7 @@ ABI_VERSION = 11
 EINVAL, EDEVICE = -1, -2
 ERR_BAD_ACTION, ERR_BAD_INDEX = 1, 2   # bits OR-ed into a call's device `err` word
 BACKUP_DEFER_GC = 4              # spl_mcts_backup_kind: SPL_BACKUP_DEFER_GC
+PLAYER_RANDOM, PLAYER_GREEDY, PLAYER_POLICY = 0, 1, 2   # spl_player_move: SPL_PLAYER_*
 
 
 class NativeEngineMissing(RuntimeError):
@@ -47,6 +48,8 @@ _SIGS = {
     "spl_score": ([C.c_void_p, C.c_int, _vp, _vp, _vp], C.c_int),
     "spl_round": ([C.c_void_p, C.c_int, _vp, _vp, _vp], C.c_int),
     "spl_tree_step": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "spl_player_move": ([C.c_void_p, C.c_int, _vp, _vp, C.c_int, _vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                         _vp, _vp, _vp, _vp], C.c_int),
     "spl_rollout_step": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint32,
                           C.c_uint32, _vp], C.c_int),
     "spl_nn_packed_floats": ([C.c_int], C.c_int),

@@ -22,6 +22,8 @@ Reference semantics kept:
 Batched form: game slots play in lockstep (every game's mover is ply % n). Each player owns
 one BatchedMCTS with one tree per game slot; at each ply only the trees of the games where
 that player is to move search (spl_mcts_set_roots_active), the others stay untouched.
+The loop asks a player object for its moves (TreePlayer here; splendor.pit seats players
+that need no tree on the same loop).
 Finished games idle (their boards take the no-op pass move, never read again). Chance is
 Philox keyed (seed, global game id, ply); deals (seed, game id, 0xFFFFFFFF).
 For n > 2 players the reference's player list is [p1, p2] only (Arena.py:86-90, an
@@ -56,6 +58,40 @@ def arena_precisions(args):
     return p
 
 
+def arena_mcts_args(args, **own):
+    """The search arguments of an arena player: args' numMCTSSims / cpuct / fpu (or the
+    player's `own`), every search full, no root noise (Coach.py:152-153, pit.py:53-60)."""
+    def pick(k, default):
+        return own[k] if own.get(k) is not None else _arg(args, k, default)
+    return dict(numMCTSSims=int(pick("numMCTSSims", 100)), cpuct=float(pick("cpuct", 1.0)),
+                fpu=float(pick("fpu", 0.0)), prob_fullMCTS=1.0,
+                ratio_fullMCTS=int(_arg(args, "ratio_fullMCTS", 5) or 1),
+                forced_playouts=bool(_arg(args, "forced_playouts", False)), dirichletAlpha=0.0,
+                temperature=list(_arg(args, "temperature", [1.25, 0.8])),
+                tempThreshold=int(_arg(args, "tempThreshold", 10)))
+
+
+class TreePlayer:
+    """One side of a batched match that moves by search: a BatchedMCTS with one tree per
+    game slot, kept through a game and emptied between games. The ply loop asks a player
+    object for `new_games(boards)` and `move(canon, active, base, ply, out)` only
+    (splendor.pit has the players that need no tree)."""
+
+    def __init__(self, mcts):
+        self.mcts = mcts
+
+    def new_games(self, boards):
+        self.mcts.set_roots(boards, keep_tree=False, force_full=True)
+
+    def move(self, canon, active, base, ply, out):
+        """Search the games with active[b] != 0 (uint8 [B]) from their canonical boards and
+        write their moves into out (int16 [B]); the other entries stay."""
+        m = self.mcts
+        m.set_roots_active(canon, active, keep_tree=True, force_full=True)
+        m.search()
+        m.pick_best(active, board_base=base, stream=ply, out=out)
+
+
 def one_vs_two(i):
     """Arena.py:200-203: 1 2 2 1  1 2 2 1 ..."""
     return (i % 4 == 0) or (i % 4 == 3)
@@ -76,12 +112,7 @@ class BatchedArena:
             prec = arena_precisions(args)
             evaluators = (evaluator_for(self.e, nnet1, self.B, precision=prec[0]),
                           evaluator_for(self.e, nnet2, self.B, precision=prec[1]))
-        margs = dict(numMCTSSims=int(_arg(args, "numMCTSSims", 100)), cpuct=float(_arg(args, "cpuct", 1.0)),
-                     fpu=float(_arg(args, "fpu", 0.0)), prob_fullMCTS=1.0,
-                     ratio_fullMCTS=int(_arg(args, "ratio_fullMCTS", 5) or 1),
-                     forced_playouts=bool(_arg(args, "forced_playouts", False)), dirichletAlpha=0.0,
-                     temperature=list(_arg(args, "temperature", [1.25, 0.8])),
-                     tempThreshold=int(_arg(args, "tempThreshold", 10)))
+        margs = arena_mcts_args(args)
         # the two players' arenas share what is free now (each would otherwise plan 80 % of it),
         # or the caller's mem_budget bytes
         budget = None
@@ -92,6 +123,7 @@ class BatchedArena:
         self.mcts = [BatchedMCTS(self.e, self.B, margs, evaluators[k], dirichlet_noise=False,
                                  seed=self.mcts_seed(k), board_base=self.game_base, mem_budget=budget)
                      for k in range(2)]
+        self.players = [TreePlayer(m) for m in self.mcts]
         self.last = None
         self.capacity = {"prunes": 0, "resets": 0, "unexpanded": 0}
 
@@ -115,8 +147,8 @@ class BatchedArena:
         base = self.game_base + g0
         boards = e.new_state(B)
         e.init(boards, None, seed=self.seed, stream=DEAL_STREAM, board_base=base)
-        for m in self.mcts:                                                   # fresh trees
-            m.set_roots(boards, keep_tree=False, force_full=True)
+        for p in self.players:                                                # fresh trees
+            p.new_games(boards)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         result = torch.zeros((B, n), dtype=torch.float32, device=dev)
         plies = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -133,11 +165,7 @@ class BatchedArena:
                 act = live & (seat_player[:, cur] == k)
                 if not bool(act.any()):
                     continue
-                a8 = act.to(torch.uint8)
-                m = self.mcts[k]
-                m.set_roots_active(canon, a8, keep_tree=True, force_full=True)
-                m.search()
-                m.pick_best(a8, board_base=base, stream=ply, out=action)
+                self.players[k].move(canon, act.to(torch.uint8), base, ply, action)
             if self.check_valid:                                               # Arena.py:158-159
                 valid = unpack_mask(e.valid_moves(canon))
                 ok = valid.gather(1, action.long().clamp(0, ACTIONS - 1).unsqueeze(1)).squeeze(1)
@@ -171,10 +199,10 @@ class BatchedArena:
             recs.append(self._play_batch(g0, min(self.B, num - g0)))
         # capacity events of both players' searches (a deviation from the reference's table)
         ev = [m.capacity_events() for m in self.mcts]
-        self.capacity = {k: sum(e[k] for e in ev) for k in ev[0]}
+        self.capacity = {k: sum(e[k] for e in ev) for k in ("prunes", "resets", "unexpanded")}
         if any(self.capacity.values()):
             import warnings
-            warnings.warn(f"BatchedArena capacity events {self.capacity}: some searches ran on pruned trees or "
+            warnings.warn(f"{type(self).__name__} capacity events {self.capacity}: some searches ran on pruned trees or "
                           f"left leaves unstored")
         last = {k: np.concatenate([r[k] for r in recs]) for k in recs[0]}
         r0 = last["result"][:, 0]

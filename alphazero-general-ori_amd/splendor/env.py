@@ -139,6 +139,24 @@ class SplendorEngine:
                                         _ptr(err), self._s()), "spl_tree_step")
         return child
 
+    def player_move(self, state, kind, active=None, pi=None, seed=0, stream=0, board_base=0, out=None,
+                    cand_out=None, best_out=None):
+        """One move of a rule-based player (_lib.PLAYER_RANDOM / _GREEDY / _POLICY;
+        SplendorPlayers.py:18-25, :93-115) on each canonical board -> int16 [B]. active (uint8
+        [B], optional): rows with 0 are skipped and keep their entries of every output. pi
+        (f32 [B,409]): the POLICY player's priors. The choice among a board's candidates is the
+        Philox draw (seed, board_base + b, stream). cand_out (int64 [B,7]) receives the packed
+        candidate sets, best_out (int32 [B]) GREEDY's best score after one move."""
+        B = state.shape[0]
+        out = out if out is not None else torch.full((B,), -1, dtype=torch.int16, device=self.device)
+        if pi is not None and (pi.dtype != torch.float32 or tuple(pi.shape) != (B, ACTIONS) or
+                               not pi.is_contiguous()):
+            raise ValueError(f"player_move: pi must be a contiguous f32 tensor of shape ({B}, {ACTIONS})")
+        _lib.check(self.L.spl_player_move(self.ctx, B, _ptr(state), _ptr(active), int(kind), _ptr(pi), seed,
+                                          int(stream), int(board_base), _ptr(out), _ptr(cand_out),
+                                          _ptr(best_out), self._s()), "spl_player_move")
+        return out
+
     def set_token_limit(self, n):
         """Board.setNumTokenLim (SplendorLogicNumba.py:214-215)."""
         _lib.check(self.L.spl_ctx_set_token_limit(self.ctx, int(n)), "spl_ctx_set_token_limit")

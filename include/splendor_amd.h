@@ -93,6 +93,31 @@ int spl_round(const spl_ctx *ctx, int B, const int8_t *state, int32_t *out, void
 int spl_tree_step(const spl_ctx *ctx, int B, const int8_t *parent, const int16_t *action,
                   int8_t *child, int32_t *err, void *hip_stream);
 
+/* The rule-based players of SplendorPlayers.py (RandomPlayer :13-21, GreedyPlayer :92-112)
+ * and an arg-max policy player, one move for each of B canonical boards (the mover is
+ * player 0, what Arena hands a player); one launch, a wave per board. With
+ * V = valid_moves(state, 0) under the context's token limit and s0 = get_score(state, 0),
+ * the candidate set C of a board is
+ *   RANDOM  V;
+ *   GREEDY  s_a = get_score(., 0) after make_move(copy, a, 0, deterministic=true) for a in
+ *           V, m = max s_a: {a in V : s_a = m} if m > s0, else V & [0,12) if non-empty, else
+ *           V & [30,60) if non-empty, else V (the fallback order of :106-111, taken
+ *           literally). The reference scores seat 1 after the move; this scores the mover;
+ *   POLICY  {a in V : pi[b][a] = max over V of pi[b]} (pi: B x 409 f32, exact equality).
+ * The action is the k-th set bit of C in action order, k = floor(u |C|), u = uniform 0 of
+ * the Philox stream (seed, board_base + b, (8 << 24) | stream).
+ * active (B u8, nullable): rows with 0 are skipped and none of their outputs is written.
+ * cand_out (B x 7 u64, packed like spl_valid_moves: C) and best_out (B i32: m for GREEDY,
+ * s0 otherwise) are nullable. SPL_EINVAL: NULL ctx / state / action, B < 0, kind outside
+ * 0..2, POLICY with NULL pi, stream > 0xFFFFFF. B == 0 launches nothing. */
+#define SPL_PLAYER_RANDOM 0
+#define SPL_PLAYER_GREEDY 1
+#define SPL_PLAYER_POLICY 2
+int spl_player_move(const spl_ctx *ctx, int B, const int8_t *state, const uint8_t *active,
+                    int kind, const float *pi, uint64_t seed, uint32_t stream,
+                    uint32_t board_base, int16_t *action, uint64_t *cand_out,
+                    int32_t *best_out, void *hip_stream);
+
 /* SplendorGame.getSymmetries (SplendorGame.py:59-61) -> Board.get_symmetries
  * (SplendorLogicNumba.py:349-395) for E examples (state E x S, pi E x 409 f32, valid E x 7
  * u64). Outputs K = 10 + 2n variant slots per example in the reference's order: identity,
