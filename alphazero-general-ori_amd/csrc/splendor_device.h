@@ -58,6 +58,17 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t x) {
 // keeps the compiler from moving memory accesses across it.
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// lane-per-board kernels that keep 64 boards in LDS (k_rollout, k_playout)
+// v of lane I of this lane's quad (DPP quad_perm broadcast; every lane must be active)
+template <int I>
+__device__ __forceinline__ int quad_bcast(int v) {
+    return __builtin_amdgcn_update_dpp(v, v, I | I << 2 | I << 4 | I << 6, 0xF, 0xF, false);
+}
+template <int N>
+struct RolloutLds {
+    static constexpr int STRIDE = (Lay<N>::ROWS % 2 ? Lay<N>::ROWS : Lay<N>::ROWS + 1) * 8;
+};
+
 // ------------------------------------------------------------------ row words
 __device__ __forceinline__ uint64_t &row(int8_t *s, int r) { return *reinterpret_cast<uint64_t *>(s + 8 * r); }
 __device__ __forceinline__ uint64_t row(const int8_t *s, int r) { return *reinterpret_cast<const uint64_t *>(s + 8 * r); }

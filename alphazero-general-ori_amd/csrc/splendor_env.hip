@@ -289,15 +289,6 @@ __global__ __launch_bounds__(THREADS) void k_player_move(int B, const int8_t *__
 #endif
 constexpr int RB = ROLLOUT_RB;   // boards per workgroup (<= 64: lane per board)
 #define RT_MARK(k) SPL_PROBE(k)
-// v of lane I of this lane's quad (DPP quad_perm broadcast; every lane must be active)
-template <int I>
-__device__ __forceinline__ int quad_bcast(int v) {
-    return __builtin_amdgcn_update_dpp(v, v, I | I << 2 | I << 4 | I << 6, 0xF, 0xF, false);
-}
-template <int N>
-struct RolloutLds {
-    static constexpr int STRIDE = (Lay<N>::ROWS % 2 ? Lay<N>::ROWS : Lay<N>::ROWS + 1) * 8;
-};
 
 // COUNT elements of a table held in registers across the workgroup's THREADS threads:
 // fetch() issues every load (clamped indices, no branch, so they all go out back to back),

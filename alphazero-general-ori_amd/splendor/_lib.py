@@ -15,6 +15,7 @@ EINVAL, EDEVICE = -1, -2
 ERR_BAD_ACTION, ERR_BAD_INDEX = 1, 2   # bits OR-ed into a call's device `err` word
 BACKUP_DEFER_GC = 4              # spl_mcts_backup_kind: SPL_BACKUP_DEFER_GC
 PLAYER_RANDOM, PLAYER_GREEDY, PLAYER_POLICY = 0, 1, 2   # spl_player_move: SPL_PLAYER_*
+PLAYOUT_UNIFORM, PLAYOUT_BUY_FIRST = 0, 1               # spl_playout: SPL_PLAYOUT_*
 
 
 class NativeEngineMissing(RuntimeError):
@@ -58,6 +59,8 @@ _SIGS = {
     "spl_nn_forward_mode": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
     "spl_rollout_run": ([C.c_void_p, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
                          C.c_uint32, C.c_uint32, _vp], C.c_int),
+    "spl_playout": ([C.c_void_p, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                     C.c_uint32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_mcts_create": ([C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)], C.c_int),
     "spl_mcts_destroy": ([C.c_void_p], C.c_int),
     "spl_mcts_device_bytes": ([C.c_void_p], C.c_longlong),

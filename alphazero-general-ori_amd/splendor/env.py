@@ -237,6 +237,42 @@ class SplendorEngine:
                                           _ptr(games_done), seed, step0, board_base, self._s()),
                    "spl_rollout_run")
 
+    PLAYOUT_POLICIES = {"uniform": _lib.PLAYOUT_UNIFORM, "buy_first": _lib.PLAYOUT_BUY_FIRST}
+
+    def playout(self, state, player=None, active=None, policy="buy_first", playouts=1, max_steps=None,
+                seed=0, step0=0, board_base=0, pi=False, steps=False, out=None):
+        """`playouts` random playouts of every board to the end of its game in one launch
+        (spl_playout) -> {"result": f32 [B,n] mean outcome in the input board's seat order,
+        "unfinished": int32 [1] playouts cut off by max_steps (default 62 n: none), "pi": f32
+        [B,409] uniform prior over the legal moves (pi=True), "steps": int32 [B,playouts]
+        moves played (steps=True)}. player (int8 [B], default 0) is each board's mover; rows
+        with active[b] == 0 (uint8 [B]) run nothing and keep their entries of every output.
+        policy: "uniform" or "buy_first" (or the _lib.PLAYOUT_* code). Playout j of row b
+        draws from Philox (seed, board_base + b playouts + j), streams step0, step0 + 1, ..
+        `out`: a dict from an earlier call whose tensors are reused."""
+        B, P, dev = state.shape[0], int(playouts), self.device
+        kind = self.PLAYOUT_POLICIES.get(policy, policy)
+        if not isinstance(kind, int):
+            raise ValueError(f"playout: policy must be one of {sorted(self.PLAYOUT_POLICIES)}, got {policy!r}")
+        for t, dt, name in ((state, torch.int8, "state"), (player, torch.int8, "player"), (active, torch.uint8, "active")):
+            if t is not None and (t.dtype != dt or t.shape[0] != B or not t.is_contiguous()):
+                raise ValueError(f"playout: {name} must be a contiguous {dt} tensor with {B} rows")
+        out = dict(out) if out is not None else {}
+        if "result" not in out:
+            out["result"] = torch.zeros((B, self.n), dtype=torch.float32, device=dev)
+        if pi and "pi" not in out:
+            out["pi"] = torch.zeros((B, ACTIONS), dtype=torch.float32, device=dev)
+        if steps and "steps" not in out:
+            out["steps"] = torch.zeros((B, P), dtype=torch.int32, device=dev)
+        if "unfinished" not in out:                              # (a reused counter keeps adding up)
+            out["unfinished"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(self.L.spl_playout(self.ctx, B, _ptr(state), _ptr(player), _ptr(active), kind, P,
+                                      int(62 * self.n if max_steps is None else max_steps), seed, int(step0),
+                                      int(board_base), _ptr(out["result"]), _ptr(out["pi"]) if pi else None,
+                                      _ptr(out["steps"]) if steps else None, _ptr(out["unfinished"]), self._s()),
+                   "spl_playout")
+        return out
+
 
 class RolloutBatch:
     """B boards of random-policy self-play, stepped by one fused launch per step

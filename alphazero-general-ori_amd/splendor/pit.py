@@ -9,11 +9,18 @@ Player specs (what pit.py's create_player builds from a name):
 * MCTSPlayer(nnet, numMCTSSims=, cpuct=, fpu=, nn_precision=, evaluator=None): a search
   player with its own BatchedMCTS and its own search arguments (pit.py:74-82, ai_1 / ai_2
   with different numMCTSSims); arguments left None come from the pit's `args`;
+* RolloutPlayer(numMCTSSims=, playouts=1, policy="buy_first", cpuct=, fpu=): a search player
+  that needs no network: the same search with uniform priors and leaf values from random
+  playouts (splendor.playout.PlayoutEvaluator, one spl_playout launch per simulation). Its
+  strength is set by simulations per move and playouts per leaf: a fixed yardstick between
+  the random and the greedy player and beyond;
 * PolicyPlayer(nnet, evaluator=None): the arg-max of the network's policy over the legal
   moves, no search;
 * GreedyPlayer(): SplendorPlayers.py:93-115, scoring the mover (DESIGN.md);
 * RandomPlayer(): SplendorPlayers.py:18-25.
 The last three move by one spl_player_move launch per ply and allocate no tree.
+A RolloutPlayer draws its playouts with its search seed (seed ^ (k + 1)), board = game_base +
+slot * playouts + playout, streams 256 c .. for its c-th simulation: a run repeats exactly.
 
 The ply loop, the game order 1 2 2 1, the seats for n > 2, the deals and chance streams, the
 check_valid assertion and the capacity warning are BatchedArena's (splendor.arena): the pit
@@ -26,12 +33,19 @@ import torch
 from . import _lib
 from .arena import BatchedArena, TreePlayer, _arg, arena_mcts_args
 from .mcts import BatchedMCTS
+from .playout import PlayoutEvaluator
 from .search import evaluator_for, nn_precision_arg
 
 
 class MCTSPlayer:
     def __init__(self, nnet, numMCTSSims=None, cpuct=None, fpu=None, nn_precision=None, evaluator=None):
         self.nnet, self.evaluator, self.nn_precision = nnet, evaluator, nn_precision
+        self.own = dict(numMCTSSims=numMCTSSims, cpuct=cpuct, fpu=fpu)
+
+
+class RolloutPlayer:
+    def __init__(self, numMCTSSims=None, playouts=1, policy="buy_first", cpuct=None, fpu=None):
+        self.playouts, self.policy = int(playouts), policy
         self.own = dict(numMCTSSims=numMCTSSims, cpuct=cpuct, fpu=fpu)
 
 
@@ -89,7 +103,7 @@ class BatchedPit(BatchedArena):
         specs = (player1, player2)
         # the networks first, then the trees share the memory that is left (as BatchedArena)
         evs = [self._evaluator(s) for s in specs]
-        trees = sum(isinstance(s, MCTSPlayer) for s in specs)
+        trees = sum(isinstance(s, (MCTSPlayer, RolloutPlayer)) for s in specs)
         budget = None
         if trees and mem_budget:
             budget = int(mem_budget) // trees
@@ -116,9 +130,14 @@ class BatchedPit(BatchedArena):
             return TreePlayer(BatchedMCTS(self.e, self.B, arena_mcts_args(self.args, **spec.own), evaluator,
                                           dirichlet_noise=False, seed=seed, board_base=self.game_base,
                                           mem_budget=budget))
+        if isinstance(spec, RolloutPlayer):
+            ev = PlayoutEvaluator(self.e, spec.playouts, spec.policy, seed=seed, board_base=self.game_base)
+            return TreePlayer(BatchedMCTS(self.e, self.B, arena_mcts_args(self.args, **spec.own), ev,
+                                          dirichlet_noise=False, seed=seed, board_base=self.game_base,
+                                          mem_budget=budget))
         if isinstance(spec, PolicyPlayer):
             return PriorPlayer(self.e, evaluator, seed)
         if isinstance(spec, (GreedyPlayer, RandomPlayer)):
             return RulePlayer(self.e, spec.kind, seed)
-        raise TypeError(f"player {k + 1}: expected MCTSPlayer, PolicyPlayer, GreedyPlayer or RandomPlayer, "
-                        f"got {type(spec).__name__}")
+        raise TypeError(f"player {k + 1}: expected MCTSPlayer, RolloutPlayer, PolicyPlayer, GreedyPlayer or "
+                        f"RandomPlayer, got {type(spec).__name__}")

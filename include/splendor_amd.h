@@ -174,6 +174,43 @@ int spl_rollout_run(const spl_ctx *ctx, int B, int K, int8_t *state, int8_t *pla
                     int32_t *games_done, uint64_t seed, uint32_t step0, uint32_t board_base,
                     void *hip_stream);
 
+/* Random playouts to the end of the game, outcomes only: the leaf evaluation of a search
+ * player that needs no network (PUCT with uniform priors, splendor/playout.py) and
+ * Monte-Carlo outcome estimates of arbitrary positions. Row b of `state` (B x S) is a board
+ * whose mover is player[b] (nullable = 0: a canonical MCTS leaf). Each row runs `playouts`
+ * (P, 1..64) independent playouts; playout j of row b is task b P + j, with Philox board id
+ * board_base + b P + j (uint32 arithmetic). Step t (0-based) of a task is spl_rollout_step's
+ * without the re-deal, on stream step0 + t: V = the mover's legality mask under the
+ * context's token limit, candidate set C, action = the k-th set bit of C in action order,
+ * k = floor(u0 |C|), make_move on the real board with chance uniforms u1 and u2, end check
+ * (u0, u1, u2 = uniforms 0, 1, 2 of the stream). C is
+ *   UNIFORM    V;
+ *   BUY_FIRST  V & {0..11, 27..29} (buy a visible card, buy a reserved card) if non-empty,
+ *              else V.
+ * A task stops at the first step after which the end vector is non-zero: that vector (seat
+ * order of the input board, no roll) is its outcome and steps = t + 1. A task that has not
+ * ended after max_steps moves contributes a zero vector, has steps = max_steps and adds 1 to
+ * *unfinished (device i32, nullable; the kernel's only global atomic); with max_steps >= 62 n
+ * no legal position can be unfinished. The input board is not end-checked before its first
+ * move (the caller excludes finished boards, as MCTS does through leaf_valid).
+ *   result    B x n f32   the sum of the row's P outcomes in f32, added in ascending j, then
+ *                         divided by (float)P (no FMA contraction: one defined value)
+ *   steps_out B x P i32   each task's steps (nullable)
+ *   pi_out    B x 409 f32 the uniform prior over V of the input board: 1.0f / (float)|V| on
+ *                         legal actions, 0 elsewhere (nullable)
+ * active (B u8, nullable): rows with 0 run nothing and none of their outputs is written.
+ * One launch; boards stay on chip for the whole playout and only the outputs are written to
+ * HBM. SPL_EINVAL before any launch: NULL ctx / state / result, B < 0, policy outside 0..1,
+ * playouts outside 1..64, max_steps outside 1..1024, step0 + max_steps > 0x80000000 (streams
+ * with the top bit set key deals). B == 0 launches nothing. */
+#define SPL_PLAYOUT_UNIFORM   0
+#define SPL_PLAYOUT_BUY_FIRST 1
+int spl_playout(const spl_ctx *ctx, int B, const int8_t *state, const int8_t *player,
+                const uint8_t *active, int policy, int playouts, int max_steps,
+                uint64_t seed, uint32_t step0, uint32_t board_base,
+                float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished,
+                void *hip_stream);
+
 
 /* ===================================================================== MCTS
  * Device-resident batched PUCT search (MCTS.py), one tree per board/game, B trees.

@@ -5,11 +5,14 @@ over many games at once and print (oneWon, twoWon, draws).
     python3 tools/pit.py --players greedy random -n 4096
     python3 tools/pit.py -p checkpoint/best.pt greedy -n 4096 -m 100 -c 2.5 -f 0.3 --json out.json
     python3 tools/pit.py -p a.pt a.pt -m1 50 -m2 200              # pit.py's ai_1 / ai_2
+    python3 tools/pit.py -p rollout:buy_first:4 greedy -n 1024 -m 100 -c 2.5 -f 0.3
 
 A player is `random`, `greedy` (SplendorPlayers.py), a checkpoint path (search with -m / -c /
 -f, as pit.py's create_player), `policy:<checkpoint>` (the network's arg-max policy, no
-search), or `init` / `policy:init` (the seeded random-init network, a floor for trained
-ones). Checkpoints load through NNetWrapper.load_checkpoint (weights only). Every game is
+search), `init` / `policy:init` (the seeded random-init network, a floor for trained
+ones), or `rollout` / `rollout:<policy>:<playouts>` (the search without a network: uniform
+priors, leaf values from <playouts> random playouts, policy uniform or buy_first; default
+buy_first:1; simulations from -m / -m1 / -m2). Checkpoints load through NNetWrapper.load_checkpoint (weights only). Every game is
 played on the device (splendor.pit.BatchedPit): --batch games at a time, Philox-keyed by
 --seed, so a run repeats exactly. --json appends the run's record (players, settings,
 wins / losses / draws, mean plies, wall seconds) to the JSON list in that file. The human and
@@ -32,6 +35,12 @@ def create_player(name, game, sims, cpuct, fpu):
         return pit.RandomPlayer()
     if name == "greedy":
         return pit.GreedyPlayer()
+    if name == "rollout" or name.startswith("rollout:"):
+        part = name.split(":")
+        if len(part) not in (1, 3):
+            raise SystemExit(f"{name}: expected rollout or rollout:<policy>:<playouts>")
+        kw = dict(policy=part[1], playouts=int(part[2])) if len(part) == 3 else {}
+        return pit.RolloutPlayer(numMCTSSims=sims, cpuct=cpuct, fpu=fpu, **kw)
     policy = name.startswith("policy:")
     path = name[len("policy:"):] if policy else name
     if os.path.isdir(path):
