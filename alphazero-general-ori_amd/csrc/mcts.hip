@@ -48,15 +48,19 @@ __device__ __noinline__ void bounds_note(int site, long long v, int t) {
 struct spl_ctx {  // must match splendor_env.hip
     int n;
     int token_limit;
+    int rules;
 };
 
 struct spl_mcts {
     int n, B, S, token_limit;
+    int rules;                           // the context's SPL_RULE_* flags at create
     SearchCfg cfg;
     Pools P;
     void *arena;
     size_t bytes;                        // the whole arena (spl_mcts_device_bytes)
 };
+// the `lim` argument of the mask-building kernels: token limit and rules (splendor_device.h)
+static inline int mcts_lim(const spl_mcts *m) { return pack_lim(m->token_limit, m->rules); }
 
 namespace {
 
@@ -3294,6 +3298,7 @@ int spl_mcts_create(const spl_ctx *ctx, int B, const spl_mcts_config *cfg, spl_m
     if (!m) return SPL_EINVAL;
     m->n = ctx->n; m->B = B; m->S = 7 * (32 + 10 * ctx->n + ctx->n * ctx->n);
     m->token_limit = ctx->token_limit;
+    m->rules = ctx->rules;
     SearchCfg &C = m->cfg;
     C.cpuct = cfg->cpuct; C.fpu = cfg->fpu; C.dir_alpha = cfg->dirichlet_alpha;
     C.dir_temp = cfg->dirichlet_temp > 0 ? cfg->dirichlet_temp : 1.0;
@@ -3376,6 +3381,8 @@ long long spl_mcts_device_bytes(const spl_mcts *m) {
     return (long long)m->bytes;
 }
 
+int spl_mcts_rules(const spl_mcts *m) { return m ? m->rules : SPL_EINVAL; }
+
 int spl_mcts_set_roots(spl_mcts *m, const int8_t *roots, int keep_tree, int force_full, void *hs) {
     return spl_mcts_set_roots_active(m, roots, nullptr, keep_tree, force_full, hs);
 }
@@ -3408,10 +3415,10 @@ int spl_mcts_pick_best(spl_mcts *m, const uint8_t *active, uint32_t board_base, 
 static int launch_select(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, uint8_t *leaf_valid,
                          int32_t *leaf_index, int32_t *leaf_count, void *hs) {
     SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_select_lanes<N>, dim3((unsigned)((m->B + 63) / 64)), dim3(64), 0,
-                                          (hipStream_t)hs, m->P, m->cfg, m->B, m->token_limit,
+                                          (hipStream_t)hs, m->P, m->cfg, m->B, mcts_lim(m),
                                           leaf_state, leaf_valid));
     SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_leaf_mask<N>, dim3((unsigned)((m->B + 63) / 64)), dim3(256), 0,
-                                          (hipStream_t)hs, m->P, m->B, m->token_limit, leaf_state, leaf_valid,
+                                          (hipStream_t)hs, m->P, m->B, mcts_lim(m), leaf_state, leaf_valid,
                                           leaf_mask, leaf_index, leaf_count));
     return check_launch();
 }
@@ -3487,7 +3494,7 @@ int spl_mcts_restart_games(spl_mcts *m, const uint8_t *restart, void *hs) {
 int spl_mcts_commit(spl_mcts *m, void *hs) {
     if (!m || !m->cfg.selfplay) return SPL_EINVAL;
     SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_commit<N>, wave_grid(m->B), dim3(THREADS), 0,
-                                          (hipStream_t)hs, m->P, m->cfg, m->B, m->token_limit));
+                                          (hipStream_t)hs, m->P, m->cfg, m->B, mcts_lim(m)));
     launch_gc(m, (hipStream_t)hs);                        // collections queued by the new searches
     return check_launch();
 }

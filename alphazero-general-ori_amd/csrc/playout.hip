@@ -23,6 +23,7 @@ using namespace spl;
 struct spl_ctx {  // must match splendor_env.hip
     int n;
     int token_limit;
+    int rules;
 };
 
 namespace {
@@ -301,8 +302,8 @@ extern "C" int spl_playout(const spl_ctx *c, int B, const int8_t *state, const i
     const dim3 grid((unsigned)(((long long)B + rpw - 1) / rpw));
 #define SPL_PLAYOUT_LAUNCH(NP)                                                                          \
     hipLaunchKernelGGL(k_playout<NP>, grid, dim3(THREADS), 0, (hipStream_t)hs, B, playouts, state,      \
-                       player, active, c->token_limit, policy, max_steps, seed, step0, board_base,      \
-                       result, pi_out, steps_out, unfinished)
+                       player, active, pack_lim(c->token_limit, c->rules), policy, max_steps, seed,     \
+                       step0, board_base, result, pi_out, steps_out, unfinished)
     switch (c->n) {
         case 2: SPL_PLAYOUT_LAUNCH(2); break;
         case 3: SPL_PLAYOUT_LAUNCH(3); break;

@@ -30,6 +30,17 @@ namespace spl {
 enum { C_ALWAYS, C_RSV_LIMIT, C_TAKE1, C_TAKE2D, C_TAKE3, C_TAKE2S, C_EX8, C_EX9, C_EX10,
        C_EX10G, C_NEVER };
 
+// The `lim` argument of every mask-building kernel carries the context's rules above the
+// token limit (<= 100): lim = token_limit | rules << 8. It is decoded where the condition
+// bits are formed (wave_valid_moves, lane_cond) and nowhere else. RULE_NO_RESERVE
+// (SPL_RULE_NO_RESERVE; ENABLE_ACTION_RESERVE = False, SplendorLogicNumba.py:508-510) clears
+// C_RSV_LIMIT, the only gate of actions 12..26; reserve + give (290..364) is gated by
+// C_EX10G and the is_limit=False reserve predicates, which do not read the switch (:260).
+constexpr int LIM_TOKEN_MASK = 0xFF, LIM_RULES_SHIFT = 8, RULE_NO_RESERVE = 1;
+__host__ __device__ constexpr int pack_lim(int token_limit, int rules) {
+    return token_limit | rules << LIM_RULES_SHIFT;
+}
+
 template <int N>
 struct Lay {  // row offsets of the (R,7) state (SplendorLogicNumba.py:296-303)
     static constexpr int NN = N + 1;                 // nobles on the table
@@ -347,12 +358,14 @@ __device__ __forceinline__ void wave_valid_moves(const int8_t *s, int p, int lim
     else if (l < 60) f = ge5(gems, ml.give);
     const uint64_t F1 = __ballot(f);
 
+    const bool no_rsv = (lim >> LIM_RULES_SHIFT) & RULE_NO_RESERVE;   // lim: token limit | rules << 8
+    lim &= LIM_TOKEN_MASK;
     const bool ex_any = T > 7;
     const bool ex8 = ex_any && T == lim - 2;
     const bool ex9 = ex_any && !ex8 && T == lim - 1;
     const bool ex10 = ex_any && !ex8 && !ex9;
     uint32_t cond = 1u << C_ALWAYS;
-    cond |= (uint32_t)(!(T == lim && bgold > 0)) << C_RSV_LIMIT;
+    cond |= (uint32_t)(!(no_rsv || (T == lim && bgold > 0))) << C_RSV_LIMIT;
     cond |= (uint32_t)(T + 1 <= lim && (T == 9 || nspec == 1)) << C_TAKE1;
     cond |= (uint32_t)(T + 2 <= lim && (T == 8 || nspec == 2)) << C_TAKE2D;
     cond |= (uint32_t)(T + 3 <= lim) << C_TAKE3;
@@ -401,12 +414,18 @@ __device__ __forceinline__ uint32_t thresh5(uint64_t w) {
 
 // condition bits (the token-count branches of wave_valid_moves)
 __device__ __forceinline__ uint32_t lane_cond(int T, int lim, int nspec, int bgold) {
+    // decoded per lane, in vector registers: as loop-invariant scalars the two decoded values
+    // are hoisted out of the move loops of k_rollout / k_playout, which are at the SGPR cap
+    // already (4 more SGPR spills each, measured 0.8 % on the env benchmark)
+    asm volatile("" : "+v"(lim));
+    const bool no_rsv = (lim >> LIM_RULES_SHIFT) & RULE_NO_RESERVE;
+    lim &= LIM_TOKEN_MASK;
     const bool ex_any = T > 7;
     const bool ex8 = ex_any && T == lim - 2;
     const bool ex9 = ex_any && !ex8 && T == lim - 1;
     const bool ex10 = ex_any && !ex8 && !ex9;
     uint32_t C = 1u << C_ALWAYS;
-    C |= (uint32_t)(!(T == lim && bgold > 0)) << C_RSV_LIMIT;
+    C |= (uint32_t)(!(no_rsv || (T == lim && bgold > 0))) << C_RSV_LIMIT;
     C |= (uint32_t)(T + 1 <= lim && (T == 9 || nspec == 1)) << C_TAKE1;
     C |= (uint32_t)(T + 2 <= lim && (T == 8 || nspec == 2)) << C_TAKE2D;
     C |= (uint32_t)(T + 3 <= lim) << C_TAKE3;

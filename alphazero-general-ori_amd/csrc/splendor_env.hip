@@ -41,6 +41,7 @@ using namespace spl;
 struct spl_ctx {
     int n;
     int token_limit;
+    int rules;          // SPL_RULE_* flags
 };
 
 namespace {
@@ -847,6 +848,8 @@ inline int check_launch() { return hipGetLastError() == hipSuccess ? 0 : SPL_EDE
 inline dim3 wave_grid(int B) { return dim3((unsigned)((B + WAVES - 1) / WAVES)); }
 inline dim3 lane_grid(int B) { return dim3((unsigned)((B + 255) / 256)); }
 inline bool ok_ctx(const spl_ctx *c) { return c && c->n >= 2 && c->n <= 4; }
+// the `lim` argument of the mask-building kernels: token limit and rules (splendor_device.h)
+inline int ctx_lim(const spl_ctx *c) { return pack_lim(c->token_limit, c->rules); }
 
 #define SPL_DISPATCH(n, CALL)            \
     switch (n) {                         \
@@ -868,6 +871,7 @@ int spl_ctx_create(int n, int token_limit, spl_ctx **out) {
     if (!c) return SPL_EINVAL;
     c->n = n;
     c->token_limit = token_limit;
+    c->rules = 0;
     *out = c;
     return 0;
 }
@@ -895,7 +899,7 @@ int spl_valid_moves(const spl_ctx *c, int B, const int8_t *state, const int8_t *
     if (!ok_ctx(c) || B < 0 || (B && (!state || !mask))) return SPL_EINVAL;
     if (!B) return 0;
     SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_valid<N>, wave_grid(B), dim3(THREADS), 0,
-                                          (hipStream_t)hs, B, state, player, c->token_limit, mask));
+                                          (hipStream_t)hs, B, state, player, ctx_lim(c), mask));
     return check_launch();
 }
 
@@ -960,7 +964,7 @@ int spl_player_move(const spl_ctx *c, int B, const int8_t *state, const uint8_t 
         return SPL_EINVAL;
     if (!B) return 0;
     SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_player_move<N>, wave_grid(B), dim3(THREADS), 0,
-                                          (hipStream_t)hs, B, state, active, kind, pi, c->token_limit,
+                                          (hipStream_t)hs, B, state, active, kind, pi, ctx_lim(c),
                                           seed, stream, board_base, action, cand_out, best_out));
     return check_launch();
 }
@@ -970,6 +974,14 @@ int spl_ctx_set_token_limit(spl_ctx *c, int token_limit) {
     c->token_limit = token_limit;
     return 0;
 }
+
+int spl_ctx_set_rules(spl_ctx *c, int flags) {
+    if (!ok_ctx(c) || (flags & ~SPL_RULE_NO_RESERVE)) return SPL_EINVAL;
+    c->rules = flags;
+    return 0;
+}
+
+int spl_ctx_rules(const spl_ctx *c) { return ok_ctx(c) ? c->rules : SPL_EINVAL; }
 
 int spl_symmetries(const spl_ctx *c, int E, const int8_t *state, const float *pi,
                    const uint64_t *valid, int8_t *out_state, float *out_pi, uint64_t *out_valid,
@@ -1016,7 +1028,7 @@ int spl_rollout_run(const spl_ctx *c, int B, int K, int8_t *state, int8_t *playe
         return SPL_EINVAL;
     if (!B || !K) return 0;
     SPL_DISPATCH(c->n, hipLaunchKernelGGL(k_rollout<N>, dim3((unsigned)((B + RB - 1) / RB)), dim3(THREADS), 0,
-                                          (hipStream_t)hs, B, K, state, player, c->token_limit,
+                                          (hipStream_t)hs, B, K, state, player, ctx_lim(c),
                                           mask_out, action_out, ended_out, games_done, seed,
                                           step0, board_base));
     return check_launch();

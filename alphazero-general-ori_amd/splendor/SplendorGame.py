@@ -12,6 +12,7 @@ reference's Numba RNG is unseeded.
 import numpy as np
 import torch
 
+from . import _lib
 from .env import ACTIONS, SplendorEngine, observation_rows, unpack_mask
 
 COLORS = ["white", "blue", "green", "red", "black", "gold"]
@@ -19,8 +20,8 @@ COLORS = ["white", "blue", "green", "red", "black", "gold"]
 
 class _BoardShim:
     """The slice of the reference's `game.board` jitclass that callers outside the engine
-    touch (Arena.py:116,173; SplendorPlayers.py:145-147): token limit + scores of the board
-    most recently passed to the game."""
+    touch (Arena.py:116,173; SplendorPlayers.py:145-147; SplendorGame.py:82-86): token limit,
+    the reserve switch + scores of the board most recently passed to the game."""
 
     def __init__(self, game):
         self._g = game
@@ -29,6 +30,17 @@ class _BoardShim:
     def setNumTokenLim(self, n):
         self._g.engine.set_token_limit(n)
         self.NUM_TOKEN_LIMIT = n
+
+    @property
+    def ENABLE_ACTION_RESERVE(self):
+        """SplendorLogicNumba.py:96, read by _valid_reserve (:508-510); assignable, as
+        SplendorGame.disableReserve / enableReserve assign it. Lives in the engine's rules."""
+        return not self._g.engine.rules & _lib.RULE_NO_RESERVE
+
+    @ENABLE_ACTION_RESERVE.setter
+    def ENABLE_ACTION_RESERVE(self, on):
+        e = self._g.engine
+        e.set_rules(flags=(e.rules & ~_lib.RULE_NO_RESERVE) | (0 if on else _lib.RULE_NO_RESERVE))
 
     def get_score(self, player):
         return self._g.getScore(self._g._last, player)
@@ -139,10 +151,13 @@ class SplendorGame:
         return move_to_str(int(move))
 
     def disableReserve(self):
-        raise NotImplementedError("ENABLE_ACTION_RESERVE=False is a training-time switch (out of scope)")
+        """SplendorGame.py:82-83: actions 12..26 are never legal from now on (the engine's
+        rules; search handles created earlier keep theirs)."""
+        self.board.ENABLE_ACTION_RESERVE = False
 
     def enableReserve(self):
-        pass
+        """SplendorGame.py:85-86."""
+        self.board.ENABLE_ACTION_RESERVE = True
 
 
 def move_to_str(a):

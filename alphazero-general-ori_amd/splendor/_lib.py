@@ -16,6 +16,7 @@ ERR_BAD_ACTION, ERR_BAD_INDEX = 1, 2   # bits OR-ed into a call's device `err` w
 BACKUP_DEFER_GC = 4              # spl_mcts_backup_kind: SPL_BACKUP_DEFER_GC
 PLAYER_RANDOM, PLAYER_GREEDY, PLAYER_POLICY = 0, 1, 2   # spl_player_move: SPL_PLAYER_*
 PLAYOUT_UNIFORM, PLAYOUT_BUY_FIRST = 0, 1               # spl_playout: SPL_PLAYOUT_*
+RULE_NO_RESERVE = 1                                     # spl_ctx_set_rules: SPL_RULE_NO_RESERVE
 
 
 class NativeEngineMissing(RuntimeError):
@@ -34,6 +35,9 @@ _SIGS = {
     "spl_ctx_create": ([C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "spl_ctx_destroy": ([C.c_void_p], C.c_int),
     "spl_ctx_set_token_limit": ([C.c_void_p, C.c_int], C.c_int),
+    "spl_ctx_set_rules": ([C.c_void_p, C.c_int], C.c_int),
+    "spl_ctx_rules": ([C.c_void_p], C.c_int),
+    "spl_mcts_rules": ([C.c_void_p], C.c_int),
     "spl_symmetries": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_symmetry_counts": ([C.c_void_p, C.c_int, _vp, _vp, _vp], C.c_int),
     "spl_gather_examples": ([C.c_void_p, C.c_int, C.c_int] + [_vp] * 14, C.c_int),

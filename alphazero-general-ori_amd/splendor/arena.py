@@ -24,6 +24,10 @@ one BatchedMCTS with one tree per game slot; at each ply only the trees of the g
 that player is to move search (spl_mcts_set_roots_active), the others stay untouched.
 The loop asks a player object for its moves (TreePlayer here; splendor.pit seats players
 that need no tree on the same loop).
+Rules: the players' search handles take the engine's rules (SplendorEngine.set_rules,
+SplendorGame.disableReserve) when the arena is created and keep them, while check_valid and the
+players that need no tree read the engine's current rules at every ply: do not change the
+engine's rules while an arena (or pit) built on it is alive.
 Finished games idle (their boards take the no-op pass move, never read again). Chance is
 Philox keyed (seed, global game id, ply); deals (seed, game id, 0xFFFFFFFF).
 For n > 2 players the reference's player list is [p1, p2] only (Arena.py:86-90, an

@@ -10,11 +10,13 @@ the same examples as a columnar `ExampleSet` and appends it to `trainExamplesHis
 `args.lazy_symmetries` it keeps the positions unexpanded (`LazySymmetryExamples`) and the
 variants are produced when training batches are assembled. `learn()`
 is Coach.learn (Coach.py:102-164): self-play iterations, training on the example history,
-the new-vs-previous BatchedArena gate and checkpoints.
+the new-vs-previous BatchedArena gate and checkpoints. `args.selfplay_reserve = False` makes
+the self-play games reserve-free while the gate plays the full game.
 """
 import numpy as np
 import torch
 
+from . import _lib
 from .env import unpack_mask
 from .arena import BatchedArena, accept_new_network
 from .examples import ExampleHistory, ExampleSet, LazySymmetryExamples
@@ -45,16 +47,24 @@ def expand_symmetries(engine, ex):
 class Coach:
     def __init__(self, game, nnet, args, batch=None, seed=0x5EED, board_base=0, mem_budget=None):
         """mem_budget: bytes of HBM the self-play search arena may plan (default: most of
-        what is free, BatchedMCTS._plan); learn() gives its arena gate the same bound."""
+        what is free, BatchedMCTS._plan); learn() gives its arena gate the same bound.
+        args.selfplay_reserve (default True): False plays self-play without the reserve moves
+        12..26 (SplendorGame.disableReserve for the self-play handle only, the reference's
+        training recipe, SplendorLogicNumba.py:96); the recorded valids and pi are the
+        reserve-free tree's. The engine's rules are the same before and after."""
         self.game, self.nnet, self.args = game, nnet, args
         B = int(batch or _arg(args, "numEps", 1))
         self.B = B
         self.seed = seed
         self.mem_budget = mem_budget
+        # args.selfplay_reserve = False: the self-play handle alone is reserve-free (the engine's
+        # own rules are put back once it exists); the gate, the pit and check_valid play the
+        # full game on the same engine: the reference's "train without, validate with"
+        rules = None if _arg(args, "selfplay_reserve", True) else game.engine.rules | _lib.RULE_NO_RESERVE
         self.sp = SelfPlay(game.engine, B, args,
                            evaluator=evaluator_for(game.engine, nnet, B, precision=nn_precision_arg(args)),
                            dirichlet_noise=float(_arg(args, "dirichletAlpha", 0.0)) > 0, seed=seed,
-                           board_base=board_base, mem_budget=mem_budget)
+                           board_base=board_base, mem_budget=mem_budget, rules=rules)
         self.sp.reset()
         self.trainExamplesHistory = ExampleHistory(_arg(args, "numItersHistory"))
 
@@ -66,7 +76,6 @@ class Coach:
         example queue every 32 iterations. Raises EngineError if a tree froze (search path
         overflow) or finished examples were dropped. Capacity events (trees pruned under
         memory pressure) are counted in self.sp.stats()."""
-        from . import _lib
         collected, done = [], 0
         start = self.sp.stats()["games_done"]
         while done < num_games:

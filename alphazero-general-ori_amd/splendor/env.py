@@ -161,6 +161,23 @@ class SplendorEngine:
         """Board.setNumTokenLim (SplendorLogicNumba.py:214-215)."""
         _lib.check(self.L.spl_ctx_set_token_limit(self.ctx, int(n)), "spl_ctx_set_token_limit")
 
+    @property
+    def rules(self):
+        """The context's rule flags (_lib.RULE_*; 0 = the full game)."""
+        r = int(self.L.spl_ctx_rules(self.ctx))
+        _lib.check(min(r, 0), "spl_ctx_rules")
+        return r
+
+    def set_rules(self, no_reserve=False, flags=None):
+        """Rule switches of every later call that builds a legality mask on this engine
+        (valid_moves, player_move, rollouts, playouts) and of search handles created from now
+        on; a BatchedMCTS keeps the rules it was created under. no_reserve: the reference's
+        ENABLE_ACTION_RESERVE = False (SplendorGame.disableReserve): actions 12..26 are never
+        legal, reserve + give (290..364) and everything else is unchanged. `flags` sets the
+        raw word (what `rules` returns) instead. The token limit is untouched."""
+        word = int(flags) if flags is not None else (_lib.RULE_NO_RESERVE if no_reserve else 0)
+        _lib.check(self.L.spl_ctx_set_rules(self.ctx, word), "spl_ctx_set_rules")
+
     def symmetries(self, state, pi, valid):
         """Board.get_symmetries for E examples -> (state [E,K,R,7], pi [E,K,409],
         valid [E,K,7], present [E,K]) with K = 10 + 2n (reference order)."""

@@ -73,7 +73,12 @@ class HashEvaluator:
 class BatchedMCTS:
     def __init__(self, engine, B, args=None, evaluator=None, dirichlet_noise=False, seed=0x5EED,
                  board_base=0, node_cap=None, edge_cap=None, selfplay=False, node_boards=None,
-                 pool_nodes=None, pool_edges=None, mem_budget=None):
+                 pool_nodes=None, pool_edges=None, mem_budget=None, rules=None):
+        """rules: the rule flags (_lib.RULE_*, SplendorEngine.set_rules) of this handle's
+        searches. None takes the engine's current rules; a given value is set on the engine
+        around the creation and the engine's own rules are restored afterwards. Either way
+        the handle keeps its rules for its lifetime (its trees store legality masks); they
+        are readable as `.rules`."""
         self.e = engine
         self.L = engine.L
         self.B = B
@@ -98,7 +103,14 @@ class BatchedMCTS:
                    mem_budget)
         self.cfg = cfg
         h = C.c_void_p()
-        _lib.check(self.L.spl_mcts_create(engine.ctx, B, C.byref(cfg), C.byref(h)), "spl_mcts_create")
+        if rules is not None:
+            own = engine.rules
+            engine.set_rules(flags=int(rules))
+        try:
+            _lib.check(self.L.spl_mcts_create(engine.ctx, B, C.byref(cfg), C.byref(h)), "spl_mcts_create")
+        finally:
+            if rules is not None:
+                engine.set_rules(flags=own)
         self.h = h
         dev = engine.device
         self.leaf_state = engine.new_state(B)
@@ -180,6 +192,11 @@ class BatchedMCTS:
         if getattr(self, "h", None) is not None:
             self.L.spl_mcts_destroy(self.h)
             self.h = None
+
+    @property
+    def rules(self):
+        """The rule flags this handle was created under (spl_mcts_rules)."""
+        return int(self.L.spl_mcts_rules(self.h))
 
     @property
     def device_bytes(self):

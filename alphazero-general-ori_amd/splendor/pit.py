@@ -22,6 +22,8 @@ The last three move by one spl_player_move launch per ply and allocate no tree.
 A RolloutPlayer draws its playouts with its search seed (seed ^ (k + 1)), board = game_base +
 slot * playouts + playout, streams 256 c .. for its c-th simulation: a run repeats exactly.
 
+Every player follows the engine's rules as they are when the pit is created (after
+game.disableReserve() nobody plays 12..26); they must not change while the pit lives (splendor.arena).
 The ply loop, the game order 1 2 2 1, the seats for n > 2, the deals and chance streams, the
 check_valid assertion and the capacity warning are BatchedArena's (splendor.arena): the pit
 only seats other player objects. Player k (0, 1) draws with seed ^ (k + 1), board =

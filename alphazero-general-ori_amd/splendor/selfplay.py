@@ -25,17 +25,18 @@ from .mcts import BatchedMCTS
 class SelfPlay(BatchedMCTS):
     """out_cap: finished-example queue (default: one full game of examples per tree, B x
     (62n + 2), so a drain per game length cannot overflow it; examples that still do not fit
-    are counted and `drain` raises)."""
+    are counted and `drain` raises). rules: as BatchedMCTS (None: the engine's current rules);
+    the games are dealt, searched and recorded (`valids`, `pi`) under the handle's rules."""
 
     def __init__(self, engine, B, args=None, evaluator=None, dirichlet_noise=True, seed=0x5EED,
                  board_base=0, out_cap=None, node_cap=None, edge_cap=None, node_boards=None,
-                 pool_nodes=None, pool_edges=None, mem_budget=None):
+                 pool_nodes=None, pool_edges=None, mem_budget=None, rules=None):
         self._selfplay_out_cap = int(out_cap or B * (62 * engine.n + 2))
         self._dropped_seen = 0
         super().__init__(engine, B, args, evaluator, dirichlet_noise=dirichlet_noise, seed=seed,
                          board_base=board_base, node_cap=node_cap, edge_cap=edge_cap, selfplay=True,
                          node_boards=node_boards, pool_nodes=pool_nodes, pool_edges=pool_edges,
-                         mem_budget=mem_budget)
+                         mem_budget=mem_budget, rules=rules)
         self.graph = None
         self.graph_k = None
 

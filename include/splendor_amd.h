@@ -50,6 +50,24 @@ int spl_ctx_create(int n_players, int token_limit, spl_ctx **out);
 int spl_ctx_destroy(spl_ctx *ctx);
 /* Board.setNumTokenLim (SplendorLogicNumba.py:214-215; Arena.py:116 handicap games) */
 int spl_ctx_set_token_limit(spl_ctx *ctx, int token_limit);
+/* Rule switches of the context: a bit set of SPL_RULE_* flags, 0 (the full game) after create.
+ * SPL_RULE_NO_RESERVE is the reference's ENABLE_ACTION_RESERVE = False (SplendorGame.
+ * disableReserve, SplendorGame.py:82-83; SplendorLogicNumba.py:96,508-510): _valid_reserve(
+ * is_limit=True) is empty, so actions 12..26 (reserve a visible card / from a deck) are never
+ * legal. Nothing else reads the switch: reserve + give one (290..364, _valid_exchange's
+ * is_limit=False call, :260) stays legal, pass (408) is still legal iff nothing else is (:263),
+ * and make_move, scores, end checks, chance and symmetries are unchanged. The mask under the
+ * rule is therefore the full mask with bits 12..26 cleared, then bit 408 set iff bits 0..407
+ * are empty. Every call that builds a legality mask from the context honours the flags at
+ * launch time: spl_valid_moves, spl_player_move, spl_rollout_step / _run, spl_playout.
+ * A search handle copies the context's rules (as its token limit) in spl_mcts_create and keeps
+ * them for its lifetime: trees store masks, so later changes of the context do not reach it.
+ * set_rules: SPL_EINVAL on a NULL context or unknown bits (nothing is changed); the token limit
+ * is untouched, and spl_ctx_set_token_limit leaves the flags alone. spl_ctx_rules /
+ * spl_mcts_rules return the flags (SPL_EINVAL on NULL). */
+#define SPL_RULE_NO_RESERVE 1
+int spl_ctx_set_rules(spl_ctx *ctx, int flags);
+int spl_ctx_rules(const spl_ctx *ctx);
 /* observation_size (SplendorLogicNumba.py:26-27): rows R; bytes per board 7*R */
 int spl_state_rows(const spl_ctx *ctx);
 int spl_state_bytes(const spl_ctx *ctx);
@@ -256,8 +274,11 @@ typedef struct {
                                 memory follows the sum of the live trees, not B x the largest */
 } spl_mcts_config;
 
+/* The handle takes the context's token limit and rules (spl_ctx_set_rules) as they are at
+ * create and keeps them: its trees store legality masks, so a handle never changes rules. */
 int spl_mcts_create(const spl_ctx *ctx, int B, const spl_mcts_config *cfg, spl_mcts **out);
 int spl_mcts_destroy(spl_mcts *m);
+int spl_mcts_rules(const spl_mcts *m);
 /* HBM bytes of the whole search arena: the shared node / edge pools, per tree its page
  * tables, transposition table (power of two >= node_cap / 0.7) and path, + self-play buffers. plan_bytes: the same figure before creating it (pool
  * sizing by the caller); device_bytes: of a created arena. */

@@ -14,7 +14,8 @@ ones), or `rollout` / `rollout:<policy>:<playouts>` (the search without a networ
 priors, leaf values from <playouts> random playouts, policy uniform or buy_first; default
 buy_first:1; simulations from -m / -m1 / -m2). Checkpoints load through NNetWrapper.load_checkpoint (weights only). Every game is
 played on the device (splendor.pit.BatchedPit): --batch games at a time, Philox-keyed by
---seed, so a run repeats exactly. --json appends the run's record (players, settings,
+--seed, so a run repeats exactly. --no-reserve plays the reserve-free game (actions 12..26
+never legal, the reference's training-time rule) for both players. --json appends the run's record (players, settings,
 wins / losses / draws, mean plies, wall seconds) to the JSON list in that file. The human and
 alpha-beta players, ratings and the board display of pit.py are out of scope."""
 import argparse
@@ -66,6 +67,8 @@ def main(argv=None):
                     help="seats of the game (seat 0 one player, every other seat the other)")
     ap.add_argument("--batch", type=int, default=None, help="games played at once (default: all)")
     ap.add_argument("--seed", type=int, default=0x5EED)
+    ap.add_argument("--no-reserve", action="store_true",
+                    help="play without the reserve moves 12..26 (SplendorGame.disableReserve)")
     ap.add_argument("--json", default=None, metavar="FILE", help="append the run's record to this JSON list")
     a = ap.parse_args(argv)
 
@@ -73,6 +76,8 @@ def main(argv=None):
     from splendor.SplendorGame import SplendorGame
     from splendor.pit import BatchedPit
     game = SplendorGame(a.num_players)
+    if a.no_reserve:
+        game.disableReserve()
     sims = [s if s is not None else a.numMCTSSims for s in (a.numMCTSSims1, a.numMCTSSims2)]
     players = [create_player(p, game, sims[k], a.cpuct, a.fpu) for k, p in enumerate(a.players)]
     batch = min(a.batch or a.num_games, a.num_games)
@@ -85,7 +90,7 @@ def main(argv=None):
     print(a.players[0], "vs", a.players[1])
     print((one, two, draws))
     rec = {"players": list(a.players), "num_players": a.num_players, "games": a.num_games, "batch": batch,
-           "seed": a.seed, "numMCTSSims": sims, "cpuct": a.cpuct, "fpu": a.fpu, "one_won": one, "two_won": two,
+           "seed": a.seed, "no_reserve": a.no_reserve, "numMCTSSims": sims, "cpuct": a.cpuct, "fpu": a.fpu, "one_won": one, "two_won": two,
            "draws": draws, "mean_plies": float(pit.last["plies"].mean()), "seconds": seconds,
            "capacity_events": pit.capacity}
     print(json.dumps(rec), flush=True)

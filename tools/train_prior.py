@@ -6,8 +6,10 @@ concurrent trees, training on the example history (GenericNNetWrapper.train's lo
 schedule, larger batches), the BatchedArena gate against the previous weights. Writes the
 accepted weights as a plain state_dict checkpoint ({"state_dict": ...}, weights-only loadable)
 and one JSON line per iteration (losses, arena result, self-play figures) to stdout:
-    python3 tools/train_prior.py OUT.pt [iterations] [games]
-bench.py --net OUT.pt then runs the headline on these weights."""
+    python3 tools/train_prior.py OUT.pt [iterations] [games] [no-reserve]
+bench.py --net OUT.pt then runs the headline on these weights. A fourth argument `no-reserve`
+plays the self-play games without the reserve moves 12..26 (args.selfplay_reserve = False,
+the reference's training recipe); the arena gate still plays the full game."""
 import json
 import os
 import sys
@@ -25,6 +27,9 @@ from splendor.coach import Coach  # noqa: E402
 out = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/trained_2p.pt"
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 games = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
+if len(sys.argv) > 4 and sys.argv[4] != "no-reserve":
+    raise SystemExit(f"{sys.argv[4]}: the fourth argument can only be no-reserve")
+selfplay_reserve = len(sys.argv) <= 4
 # (Coach.learn's checkpoints and example history stay out of gpurun_out: only OUT is kept)
 folder = os.path.join(os.environ.get("TMPDIR", "/tmp"), "train_prior_ckpt")
 g = SplendorGame(2)
@@ -32,7 +37,8 @@ torch.manual_seed(0)
 nn = NNetWrapper(g, dict(epochs=2, batch_size=512, learn_rate=1e-3, dropout=0.3), seed=0)
 args = dict(numMCTSSims=100, cpuct=2.5, fpu=0.3, prob_fullMCTS=0.25, ratio_fullMCTS=5, forced_playouts=False,
             dirichletAlpha=0.3, temperature=[1.25, 0.8], tempThreshold=10, numIters=1, numEps=games,
-            numItersHistory=3, arenaCompare=256, updateThreshold=0.55, checkpoint=folder)
+            numItersHistory=3, arenaCompare=256, updateThreshold=0.55, checkpoint=folder,
+            selfplay_reserve=selfplay_reserve)
 coach = Coach(g, nn, args, batch=games, seed=0x7A11)
 last = {}
 orig_train = nn.train
