@@ -11,6 +11,7 @@
 #include "../../include/splendor_amd.h"
 
 #include "mcts_device.h"
+#include "nn_stage.h"
 
 using namespace spl;
 
@@ -2058,21 +2059,40 @@ __device__ unsigned long long g_lm_probe[LM_PSLOTS][8];
 #else
 #define LMPROBE(k)
 #endif
-template <int N>
+// STG (spl_mcts_select_staged / spl_nn_stage_leaves): the kernel also fills the staged leaf
+// buffer `stage` (nn_stage.h; layout in splendor_amd.h) for k_nn_forward's staged mode, in the
+// list order above (segments in order, trees ascending inside a segment): list entry p = (the
+// NN leaves of all earlier segments) + (the leaf's rank in its own). The first term is the number
+// of non-zero bytes of leaf_valid[0 .. 64 j), counted by the workgroup itself (16-byte loads,
+// all in flight beside the board loads; one block reduction through the first barrier), so the
+// select kernel stays as it is. Entry p gets its tree row, its seven mask words and its board as
+// the seven int8 columns of slot p % 32 of tile p / 32 — the network kernel's LDS image — built
+// from the 8-byte LDS rows, four rows of one column per dword store. The last segment writes the
+// total.
+// bytes of x that are not zero, x's bytes taken as counts 0 / non-0
+__device__ __forceinline__ int nonzero_bytes(uint32_t x) {
+    return __popc((((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u);
+}
+template <int N, bool STG = false>
 __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, const int8_t *__restrict__ leaf_state,
                                                    const uint8_t *__restrict__ leaf_valid,
                                                    uint64_t *__restrict__ leaf_mask,
                                                    int32_t *__restrict__ leaf_index,
-                                                   int32_t *__restrict__ leaf_count) {
+                                                   int32_t *__restrict__ leaf_count,
+                                                   char *__restrict__ stage) {
     using Lx = Lay<N>;
     using Cv = Conv<N>;
     constexpr int RB = 64, ST = (Lx::ROWS % 2 ? Lx::ROWS : Lx::ROWS + 1) * 8;
+    static_assert(Lx::ROWS == nnstage::rows(N) && 4 * ((Lx::ROWS + 3) / 4) <= nnstage::x0s(N) &&
+                      nnstage::TILE == 32, "staged tile image (nn_stage.h)");
     __shared__ __align__(16) int8_t lds[RB * ST];
     __shared__ uint64_t mfac[7 * 116];
     __shared__ uint64_t pf0[4][RB], pf1[RB];
     __shared__ uint32_t pcond[RB];
     __shared__ uint8_t pbad[4][RB];
     __shared__ uint64_t msk[RB][7];
+    __shared__ int wsum[4];                              // (STG) the waves' counts of earlier leaves
+    __shared__ int8_t lst[STG ? RB : 1], rnk[STG ? RB : 1];   // (STG) rank -> leaf, leaf -> rank / -1
     LMPROBE(0)
     const int b0 = blockIdx.x * RB, nb = min(RB, B - b0);
     const int tid = threadIdx.x, w = tid >> 6, l = lane_id();
@@ -2081,6 +2101,27 @@ __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, cons
         const uint64_t bv = __ballot(v);
         if (v) leaf_index[b0 + __popcll(bv & lanemask_lt())] = b0 + l;
         if (l == 0) leaf_count[blockIdx.x] = __popcll(bv);
+    }
+    int pre = 0, rank = 0, nlist = 0;                    // (STG)
+    bool vme = false;
+    if constexpr (STG) {
+        // leaf_valid[0 .. 64 blockIdx.x): 4 16-byte units per earlier segment, VB per thread in
+        // flight, 512 segments per pass
+        constexpr int VB = 8;
+        const int nu = blockIdx.x * 4;
+        const uint4 *vv = reinterpret_cast<const uint4 *>(leaf_valid);
+        for (int u0 = 0; u0 < nu; u0 += 256 * VB) {
+            uint4 q[VB];
+#pragma unroll
+            for (int k = 0; k < VB; k++) {
+                const int u = u0 + 256 * k + tid;
+                q[k] = u < nu ? vv[u] : uint4{0u, 0u, 0u, 0u};
+            }
+#pragma unroll
+            for (int k = 0; k < VB; k++)
+                pre += nonzero_bytes(q[k].x) + nonzero_bytes(q[k].y) + nonzero_bytes(q[k].z) + nonzero_bytes(q[k].w);
+        }
+        vme = l < nb && leaf_valid[b0 + l];
     }
     // the boards and the mask factors: every load issued before the first LDS store (a loop of
     // load -> store pairs waits one round trip per iteration — 17 of this kernel's 19 us at
@@ -2116,8 +2157,65 @@ __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, cons
 #pragma unroll
     for (int k = 0; k < FW; k++)
         if (tid + 256 * k < 7 * 116) mfac[tid + 256 * k] = fw[k];
+    if constexpr (STG) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
+        const uint64_t bv = __ballot(vme);
+        rank = __popcll(bv & lanemask_lt());
+        nlist = __popcll(bv);
+        if (w == 0) {
+            if (l == 0) wsum[0] = pre;
+            if (vme) lst[rank] = (int8_t)l;
+            rnk[l] = vme ? (int8_t)rank : (int8_t)-1;
+        } else if (l == 0) {
+            wsum[w] = pre;
+        }
+    }
     lds_sync();
     LMPROBE(1)
+    int base = 0;                                        // (STG) list entries of earlier segments
+    if constexpr (STG) {
+        base = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        constexpr int G = (Lx::ROWS + 3) / 4, X0S = nnstage::x0s(N), TB = nnstage::tile_bytes(N);
+        char *sx = stage + nnstage::x_off(B);
+        for (int it = tid; it < nlist * G; it += 256) {  // rows 4 g .. 4 g + 3 of list entry base + q
+            const int q = it / G, g = it - q * G, p = base + q;
+            const uint64_t *rw = reinterpret_cast<const uint64_t *>(lds + lst[q] * ST) + 4 * g;
+            uint32_t lo[4], hi[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint64_t a = 4 * g + j < Lx::ROWS ? rw[j] : 0ull;
+                lo[j] = (uint32_t)a;
+                hi[j] = (uint32_t)(a >> 32);
+            }
+            // 4 x 8 byte transpose on v_perm_b32 (selector bytes 0-3: second operand, 4-7: first):
+            // byte pairs of rows (0, 1) and (2, 3), then the column's four bytes
+            uint32_t col[7];
+            {
+                const uint32_t t01 = __builtin_amdgcn_perm(lo[1], lo[0], 0x05010400u), t23 = __builtin_amdgcn_perm(lo[3], lo[2], 0x05010400u);
+                const uint32_t u01 = __builtin_amdgcn_perm(lo[1], lo[0], 0x07030602u), u23 = __builtin_amdgcn_perm(lo[3], lo[2], 0x07030602u);
+                col[0] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
+                col[1] = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+                col[2] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);
+                col[3] = __builtin_amdgcn_perm(u23, u01, 0x07060302u);
+            }
+            {
+                const uint32_t t01 = __builtin_amdgcn_perm(hi[1], hi[0], 0x05010400u), t23 = __builtin_amdgcn_perm(hi[3], hi[2], 0x05010400u);
+                const uint32_t u01 = __builtin_amdgcn_perm(hi[1], hi[0], 0x07030602u), u23 = __builtin_amdgcn_perm(hi[3], hi[2], 0x07030602u);
+                col[4] = __builtin_amdgcn_perm(t23, t01, 0x05040100u);
+                col[5] = __builtin_amdgcn_perm(t23, t01, 0x07060302u);
+                col[6] = __builtin_amdgcn_perm(u23, u01, 0x05040100u);
+            }
+            if (p < B) {
+                uint32_t *dst = reinterpret_cast<uint32_t *>(sx + (size_t)(p >> 5) * TB + (p & 31) * X0S) + g;
+#pragma unroll
+                for (int c = 0; c < 7; c++) dst[c * (32 * X0S / 4)] = col[c];
+            }
+        }
+        if (w == 0 && vme && base + rank < B)
+            reinterpret_cast<int32_t *>(stage + nnstage::ROWS_OFF)[base + rank] = b0 + l;
+        if (blockIdx.x == gridDim.x - 1 && tid == 0) *reinterpret_cast<int32_t *>(stage) = base + nlist;
+    }
     if (l < nb) {                                        // predicates: part w of every leaf
         uint64_t f0, f1;
         uint32_t cc;
@@ -2174,8 +2272,20 @@ __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, cons
     }
     lds_sync();
     LMPROBE(4)
-    for (int i = tid; i < nb * 7; i += 256)
-        if (leaf_valid[b0 + i / 7]) leaf_mask[(size_t)b0 * 7 + i] = (&msk[0][0])[i];
+    if constexpr (STG) {
+        uint64_t *smask = reinterpret_cast<uint64_t *>(stage + nnstage::mask_off(B));
+        for (int i = tid; i < nb * 7; i += 256) {
+            const int lf = i / 7, r = rnk[lf];
+            if (r >= 0) {
+                const uint64_t mw = (&msk[0][0])[i];
+                leaf_mask[(size_t)b0 * 7 + i] = mw;
+                if (base + r < B) smask[(size_t)(base + r) * 7 + (i - 7 * lf)] = mw;
+            }
+        }
+    } else {
+        for (int i = tid; i < nb * 7; i += 256)
+            if (leaf_valid[b0 + i / 7]) leaf_mask[(size_t)b0 * 7 + i] = (&msk[0][0])[i];
+    }
     LMPROBE(5)
 }
 
@@ -3417,10 +3527,45 @@ static int launch_select(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, u
     SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_select_lanes<N>, dim3((unsigned)((m->B + 63) / 64)), dim3(64), 0,
                                           (hipStream_t)hs, m->P, m->cfg, m->B, mcts_lim(m),
                                           leaf_state, leaf_valid));
+    char *no_stage = nullptr;
     SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_leaf_mask<N>, dim3((unsigned)((m->B + 63) / 64)), dim3(256), 0,
                                           (hipStream_t)hs, m->P, m->B, mcts_lim(m), leaf_state, leaf_valid,
-                                          leaf_mask, leaf_index, leaf_count));
+                                          leaf_mask, leaf_index, leaf_count, no_stage));
     return check_launch();
+}
+
+// k_leaf_mask with the staged leaf buffer (B > 0; arguments checked by the callers)
+static int launch_mask_staged(int n, const Pools &P, int B, int lim, const int8_t *leaf_state,
+                              const uint8_t *leaf_valid, uint64_t *leaf_mask, void *stage, void *hs) {
+    int32_t *no_list = nullptr;
+    char *st = static_cast<char *>(stage);
+    SPL_DISPATCH(n, hipLaunchKernelGGL((k_leaf_mask<N, true>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0,
+                                       (hipStream_t)hs, P, B, lim, leaf_state, leaf_valid, leaf_mask, no_list,
+                                       no_list, st));
+    return check_launch();
+}
+static bool stage_args_ok(const void *leaf_state, const void *leaf_mask, const void *leaf_valid, const void *stage) {
+    return leaf_state && leaf_mask && leaf_valid && stage && reinterpret_cast<uintptr_t>(leaf_state) % 4 == 0 &&
+           reinterpret_cast<uintptr_t>(leaf_mask) % 8 == 0 && reinterpret_cast<uintptr_t>(leaf_valid) % 16 == 0 &&
+           reinterpret_cast<uintptr_t>(stage) % 16 == 0;
+}
+
+int spl_mcts_select_staged(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, uint8_t *leaf_valid, void *stage,
+                           void *hs) {
+    if (!m || !stage_args_ok(leaf_state, leaf_mask, leaf_valid, stage)) return SPL_EINVAL;
+    SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_select_lanes<N>, dim3((unsigned)((m->B + 63) / 64)), dim3(64), 0,
+                                          (hipStream_t)hs, m->P, m->cfg, m->B, mcts_lim(m),
+                                          leaf_state, leaf_valid));
+    return launch_mask_staged(m->n, m->P, m->B, mcts_lim(m), leaf_state, leaf_valid, leaf_mask, stage, hs);
+}
+
+int spl_nn_stage_leaves(const spl_ctx *ctx, int B, const int8_t *leaf_state, const uint8_t *leaf_valid,
+                        uint64_t *leaf_mask, void *stage, void *hs) {
+    if (!ctx || ctx->n < 2 || ctx->n > 4 || B < 0 || !stage_args_ok(leaf_state, leaf_mask, leaf_valid, stage))
+        return SPL_EINVAL;
+    if (!B) return 0;
+    return launch_mask_staged(ctx->n, Pools{}, B, pack_lim(ctx->token_limit, ctx->rules), leaf_state, leaf_valid,
+                              leaf_mask, stage, hs);
 }
 
 int spl_mcts_select(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, uint8_t *leaf_valid,

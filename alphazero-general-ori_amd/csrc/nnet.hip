@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/splendor_amd.h"
+#include "nn_stage.h"
 
 // per-layer cycle probes (diagnostic builds only, -DNN_PROBE=1; never the product): wave 0's
 // s_memtime at every layer boundary, summed over the workgroups (spl_diag_nn_probe)
@@ -154,6 +155,13 @@ struct Net {
     static constexpr int stg_nc(int s) { return stg_index(s) ? CL[stg_layer(s)] - first(stg_layer(s)) : first(stg_layer(s)); }
 };
 static_assert(Net<4>::XR + RING <= BUFA, "input staging + weight ring fit bufA");
+// the staged leaf buffer (nn_stage.h; written by k_leaf_mask): its tiles are this kernel's input image
+static_assert(ML == nnstage::TILE, "staged tiles are this kernel's tiles");
+static_assert(Net<2>::R == nnstage::rows(2) && Net<3>::R == nnstage::rows(3) && Net<4>::R == nnstage::rows(4), "board rows");
+static_assert(Net<2>::X0S == nnstage::x0s(2) && Net<3>::X0S == nnstage::x0s(3) && Net<4>::X0S == nnstage::x0s(4),
+              "staged image stride");
+static_assert(Net<2>::XR == nnstage::tile_bytes(2) && Net<3>::XR == nnstage::tile_bytes(3) &&
+                  Net<4>::XR == nnstage::tile_bytes(4), "a staged tile is the whole input image");
 
 template <int V> struct IntC {
     static constexpr int value = V;
@@ -444,18 +452,24 @@ __device__ __forceinline__ int nn_list_rows(const int32_t *__restrict__ count, i
 // the MFMAs, 3 (SPL_NN_F32: the six products above), 2 (SPL_NN_BF16X2: hi hi, hi mid, mid hi) or
 // 1 (SPL_NN_BF16: hi hi); parts that are not multiplied are not loaded (weights) or not read
 // (split activations). Everything between the GEMMs is f32 on their untruncated outputs.
-template <int NP, int PR>
+// STG (spl_nn_forward_staged): the tile's input comes from the staged leaf buffer k_leaf_mask
+// filled (nn_stage.h) — the listed leaves' total, the tile's finished int8 image, its masks and
+// its output rows at fixed addresses, one round trip; no list scan, no index hop, no scatter.
+template <int NP, int PR, bool STG = false>
 // one workgroup per CU (LDS) = 2 waves per SIMD: the register budget is 256, and without
 // saying so the scheduler sinks the prefetched weight loads next to their MFMAs
 // idx / count (optional): the kernel evaluates the search's NN leaves as k_leaf_mask lists
 // them (nn_list_rows: B trees in segments of 64) — board / mask / output row idx[...] —
 // instead of rows 0 .. B; tiles past the list's end exit at once.
+// sbuf (STG only): the staged leaf buffer; state / mask / idx / count are then not read, and
+// nn_list_rows and the byte scatter are not instantiated.
 __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_nn_forward(int B, const int8_t *__restrict__ state,
                                                     const uint64_t *__restrict__ mask,
                                                     const float *__restrict__ W, float *__restrict__ pi_out,
                                                     float *__restrict__ v_out,
                                                     const int32_t *__restrict__ idx,
-                                                    const int32_t *__restrict__ count) {
+                                                    const int32_t *__restrict__ count,
+                                                    const char *__restrict__ sbuf) {
     using Nt = Net<NP>;
     constexpr int R = Nt::R, X0S = Nt::X0S, NSTG = Nt::NSTG;
     // all LDS in one array (a second __shared__ object beside LDS-DMA targets can make the
@@ -489,6 +503,8 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                         glds16(src + ((b * C + C0 + j) * 3 + p) * 1024, dst + ((j * 4 + b) * 3 + p) * 1024);
         }
     };
+    int scnt = 0;                                        // (staged: one scalar load, in flight
+    if constexpr (STG) scnt = *reinterpret_cast<const int32_t *>(sbuf);    //  beside wave 7's stages)
     if (w == 7) {                                        // (first: the weights do not depend on
         load_stage(IntC<0>());                           //  the tile's leaves)
         load_stage(IntC<1>());
@@ -499,7 +515,9 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int *rowt = reinterpret_cast<int *>(lds + BUFA + SAB + ML * 7 * 8);
     int *rowt_w = rowt + (w < 7 ? w : 0) * ML, *rowv = rowt + 7 * ML, *offv_w = rowt + (8 + (w < 7 ? w : 0)) * ML;
     int cnt = B;
-    if (count) {
+    if constexpr (STG) {
+        cnt = min(__builtin_amdgcn_readfirstlane(scnt), B);
+    } else if (count) {
         cnt = __builtin_amdgcn_readfirstlane(
             nn_list_rows(count, (B + 63) >> 6, b0, w < 7 ? rowt_w : nullptr, offv_w));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the wave's own LDS writes,
@@ -513,7 +531,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // row of leaf i of this tile (its board, mask and outputs): rowin while the wave stages the
     // input, rowof in the epilogues
     const auto rowin = [&](int i) -> size_t { return count ? (size_t)idx[rowt_w[i]] : (size_t)(b0 + i); };
-    const auto rowof = [&](int i) -> size_t { return count ? (size_t)rowv[i] : (size_t)(b0 + i); };
+    const auto rowof = [&](int i) -> size_t { return STG || count ? (size_t)rowv[i] : (size_t)(b0 + i); };
 
 #if NN_PROBE
     uint64_t nlast = __builtin_readcyclecounter();
@@ -526,7 +544,41 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     int8_t *x0 = reinterpret_cast<int8_t *>(lds);
     // (waves 0-6 stage the input, so wave 7's vmcnt counts its LDS-DMA only)
     constexpr int NS7 = NNT - 64;
-    if (w < 7) {
+    if constexpr (STG) {
+        if (w < 7) {
+            // the tile's image as k_leaf_mask left it (x0's layout, 16-byte units), its masks and
+            // its rows: contiguous, every load issued before the first LDS store
+            constexpr int UN = 7 * ML * X0S / 16, PER = (UN + NS7 - 1) / NS7;
+            const u32x4 *src = reinterpret_cast<const u32x4 *>(sbuf + nnstage::x_off(B)) + (size_t)blockIdx.x * UN;
+            const uint64_t *smask = reinterpret_cast<const uint64_t *>(sbuf + nnstage::mask_off(B)) + (size_t)b0 * 7;
+            const int32_t *srows = reinterpret_cast<const int32_t *>(sbuf + nnstage::ROWS_OFF) + b0;
+            const u32x4 d0 = src[min(tid, UN - 1)], d1 = src[min(tid + NS7, UN - 1)];
+            const u32x4 d2 = PER > 2 ? src[min(tid + 2 * NS7, UN - 1)] : d1;
+            static_assert(PER <= 3, "tile image: at most three 16-byte units per thread");
+            const uint64_t mk = smask[min(tid, nb * 7 - 1)];
+            const int rw = srows[min(lane, nb - 1)];
+            // per-column biases (as below), two per thread
+            static_assert(4 * 128 <= 2 * NS7, "per-column biases: two per thread");
+            const int t1 = min(tid + NS7, 4 * 128 - 1);
+            const auto bias_of = [&](int t) {
+                const int l = t >> 7, c = t & 127;
+                return l == 2 ? (c >= 8 ? W[Nt::boff(2) + c - 8] : 0.f) : W[Nt::boff(l) + c];
+            };
+            const float bl0 = bias_of(tid), bl1 = bias_of(t1);
+            u32x4 *xl = reinterpret_cast<u32x4 *>(lds);
+            if (tid < UN) xl[tid] = d0;
+            if (tid + NS7 < UN) xl[tid + NS7] = d1;
+            if (PER > 2 && tid + 2 * NS7 < UN) xl[tid + 2 * NS7] = d2;
+            if (tid < nb * 7) mskl[tid] = mk;
+            if (w == 0 && lane < nb) rowv[lane] = rw;
+            biasL[tid] = bl0;
+            if (tid + NS7 < 4 * 128) biasL[tid + NS7] = bl1;
+        } else {
+            constexpr int N1 = 4 * PR * Nt::stg_nc(1);       // (wave 7: as below)
+            static_assert(N1 < 64, "vmcnt range");
+            __builtin_amdgcn_s_waitcnt((N1 & 15) | ((N1 >> 4) << 14) | (7 << 4) | (15 << 8));
+        }
+    } else if (w < 7) {
         if (tid < nb * 7) mskl[tid] = mask[rowin(tid / 7) * 7 + tid % 7];
         // per-column biases; partialgpool_1's outputs land on channels 8..127 (its 8 pooled
         // channels come first), so its bias is shifted by 8
@@ -1023,19 +1075,20 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 inline int check_launch() { return hipGetLastError() == hipSuccess ? 0 : SPL_EDEVICE; }
 
 // the instantiation of (players 2 .. 4, precision mode 0 .. 2: 3 - mode parts per operand)
-template <int NP>
+template <int NP, bool STG>
 const void *nn_kernel_np(int precision) {
     switch (precision) {
-        case SPL_NN_F32: return reinterpret_cast<const void *>(&k_nn_forward<NP, 3>);
-        case SPL_NN_BF16X2: return reinterpret_cast<const void *>(&k_nn_forward<NP, 2>);
-        default: return reinterpret_cast<const void *>(&k_nn_forward<NP, 1>);
+        case SPL_NN_F32: return reinterpret_cast<const void *>(&k_nn_forward<NP, 3, STG>);
+        case SPL_NN_BF16X2: return reinterpret_cast<const void *>(&k_nn_forward<NP, 2, STG>);
+        default: return reinterpret_cast<const void *>(&k_nn_forward<NP, 1, STG>);
     }
 }
-inline const void *nn_kernel(int n_players, int precision) {
+template <bool STG>
+const void *nn_kernel(int n_players, int precision) {
     switch (n_players) {
-        case 2: return nn_kernel_np<2>(precision);
-        case 3: return nn_kernel_np<3>(precision);
-        default: return nn_kernel_np<4>(precision);
+        case 2: return nn_kernel_np<2, STG>(precision);
+        case 3: return nn_kernel_np<3, STG>(precision);
+        default: return nn_kernel_np<4, STG>(precision);
     }
 }
 
@@ -1073,8 +1126,9 @@ static int launch_nn(int n_players, int B, const int8_t *leaf_state, const uint6
         return SPL_EINVAL;
     if (precision < SPL_NN_F32 || precision > SPL_NN_BF16) return SPL_EINVAL;
     if (!B) return 0;
-    const void *kernel = nn_kernel(n_players, precision);
-    void *args[] = {&B, &leaf_state, &leaf_mask, &packed_weights, &pi, &v, &idx, &count};
+    const void *kernel = nn_kernel<false>(n_players, precision);
+    const char *stage = nullptr;
+    void *args[] = {&B, &leaf_state, &leaf_mask, &packed_weights, &pi, &v, &idx, &count, &stage};
     if (hipLaunchKernel(kernel, dim3((unsigned)((B + ML - 1) / ML)), dim3(NNT), args, 0, (hipStream_t)hs) != hipSuccess)
         return SPL_EDEVICE;
     return check_launch();
@@ -1099,6 +1153,28 @@ int spl_nn_forward_mode(int n_players, int B, const int8_t *leaf_state, const ui
     if (!leaf_index != !leaf_count || (leaf_count && reinterpret_cast<uintptr_t>(leaf_count) % 16)) return SPL_EINVAL;
     return launch_nn(n_players, B, leaf_state, leaf_mask, packed_weights, pi, v, leaf_index, leaf_count, precision,
                      hs);
+}
+
+long long spl_nn_stage_bytes(int n_players, int B) {
+    if (n_players < 2 || n_players > 4 || B < 0) return SPL_EINVAL;
+    return (long long)nnstage::bytes(n_players, B);
+}
+
+int spl_nn_forward_staged(int n_players, int B, const void *stage, const float *packed_weights, float *pi, float *v,
+                          int precision, void *hs) {
+    if (n_players < 2 || n_players > 4 || B < 0 || !stage || !packed_weights || !pi || !v) return SPL_EINVAL;
+    if (reinterpret_cast<uintptr_t>(stage) % 16 || reinterpret_cast<uintptr_t>(packed_weights) % 16) return SPL_EINVAL;
+    if (precision < SPL_NN_F32 || precision > SPL_NN_BF16) return SPL_EINVAL;
+    if (!B) return 0;
+    const void *kernel = nn_kernel<true>(n_players, precision);
+    const int8_t *no_state = nullptr;
+    const uint64_t *no_mask = nullptr;
+    const int32_t *no_list = nullptr;
+    const char *st = static_cast<const char *>(stage);
+    void *args[] = {&B, &no_state, &no_mask, &packed_weights, &pi, &v, &no_list, &no_list, &st};
+    if (hipLaunchKernel(kernel, dim3((unsigned)((B + ML - 1) / ML)), dim3(NNT), args, 0, (hipStream_t)hs) != hipSuccess)
+        return SPL_EDEVICE;
+    return check_launch();
 }
 
 }  // extern "C"

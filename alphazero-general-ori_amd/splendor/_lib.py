@@ -61,6 +61,10 @@ _SIGS = {
     "spl_nn_forward": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_nn_forward_indexed": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_nn_forward_mode": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
+    "spl_nn_stage_bytes": ([C.c_int, C.c_int], C.c_longlong),
+    "spl_nn_stage_leaves": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "spl_nn_forward_staged": ([C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
+    "spl_mcts_select_staged": ([C.c_void_p, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_rollout_run": ([C.c_void_p, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
                          C.c_uint32, C.c_uint32, _vp], C.c_int),
     "spl_playout": ([C.c_void_p, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,

@@ -117,8 +117,12 @@ class BatchedMCTS:
         self.leaf_mask = torch.zeros((B, MASK_WORDS), dtype=torch.int64, device=dev)
         self.leaf_valid = torch.zeros(B, dtype=torch.uint8, device=dev)
         self.leaf_index = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.leaf_count = torch.zeros((B + 63) // 64, dtype=torch.int32, device=dev)   # per 64-tree segment
+        self._leaf_count = torch.zeros((B + 63) // 64, dtype=torch.int32, device=dev)   # per 64-tree segment
         self.evaluator = evaluator or HashEvaluator(engine)
+        # the staged leaf buffer (spl_nn_stage_bytes): the mask kernel writes the network's tiles
+        # in list order for an evaluator that reads them (`staged`, the fused network)
+        self.stage = None                                   # (allocated with the first such select)
+        self._staged_select = False
         self._hdr = torch.empty((B, HDR_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
 
     MEM_FRACTION = 0.8      # of the device's free memory a default-sized arena may take
@@ -238,6 +242,27 @@ class BatchedMCTS:
                                              self.e._s()), "spl_mcts_pick_best")
         return out
 
+    # the network reads its leaves from the staged buffer (SPLENDOR_NN_STAGED=0: from the
+    # compacted index list, spl_mcts_select_compact + spl_nn_forward_indexed; for A/B checks)
+    NN_STAGED = os.environ.get("SPLENDOR_NN_STAGED", "1") != "0"
+
+    @property
+    def leaf_count(self):
+        """NN leaves of the last select: per 64-tree segment on the indexed path, the one total
+        of the staged buffer's header on the staged path (int32, device; .sum() is the number of
+        listed leaves either way)."""
+        return self.stage[:4].view(torch.int32) if self._staged_select else self._leaf_count
+
+    def _stage_buf(self):
+        """The staged leaf buffer if the evaluator reads one (allocated and zero-filled once, in
+        the first, eager call), else None."""
+        if not (self.NN_STAGED and getattr(self.evaluator, "staged", False)):
+            return None
+        if self.stage is None:
+            from .nnet import new_stage
+            self.stage = new_stage(self.e.n, self.B, self.e.device)
+        return self.stage
+
     def search(self):
         """Run simulations until every tree has spent its budget."""
         for _ in range(int(self.headers()["budget"].max())):
@@ -248,17 +273,27 @@ class BatchedMCTS:
 
     def simulate(self, defer_gc=False):
         """One simulation on every tree with budget left: select -> evaluate -> backup. An
-        evaluator that can take a compacted leaf list (`indexed`, the fused network) runs on
+        evaluator that can take the NN leaves alone — from the staged leaf buffer (`staged`,
+        preferred) or a compacted leaf list (`indexed`); the fused network does both — runs on
         the trees whose leaf needs the network only; the trees whose leaf is terminal are
         backed up meanwhile on a side stream (trees are independent; spl_mcts_backup_kind).
         defer_gc (self-play): the caller commits before the next select, and that commit's
         collection takes the withdrawn simulations' trees (SPL_BACKUP_DEFER_GC)."""
         s = self.e._s()
         dg = _lib.BACKUP_DEFER_GC if defer_gc else 0
-        if getattr(self.evaluator, "indexed", False):
-            _lib.check(self.L.spl_mcts_select_compact(self.h, _ptr(self.leaf_state), _ptr(self.leaf_mask),
-                                                      _ptr(self.leaf_valid), _ptr(self.leaf_index),
-                                                      _ptr(self.leaf_count), s), "spl_mcts_select_compact")
+        stage = self._stage_buf()
+        self._staged_select = stage is not None
+        if stage is not None or getattr(self.evaluator, "indexed", False):
+            if stage is not None:
+                _lib.check(self.L.spl_mcts_select_staged(self.h, _ptr(self.leaf_state), _ptr(self.leaf_mask),
+                                                         _ptr(self.leaf_valid), _ptr(stage), s),
+                           "spl_mcts_select_staged")
+                how = dict(stage=stage)
+            else:
+                _lib.check(self.L.spl_mcts_select_compact(self.h, _ptr(self.leaf_state), _ptr(self.leaf_mask),
+                                                          _ptr(self.leaf_valid), _ptr(self.leaf_index),
+                                                          _ptr(self._leaf_count), s), "spl_mcts_select_compact")
+                how = dict(index=self.leaf_index, count=self._leaf_count)
             if self.OVERLAP_TERMINAL and self.e.device.type == "cuda":
                 cur = torch.cuda.current_stream(self.e.device)
                 side = getattr(self, "_side", None)
@@ -267,14 +302,12 @@ class BatchedMCTS:
                 side.wait_stream(cur)
                 _lib.check(self.L.spl_mcts_backup_kind(self.h, None, None, None, 2, C.c_void_p(side.cuda_stream)),
                            "spl_mcts_backup_kind")
-                pi, v = self.evaluator(self.leaf_state, self.leaf_mask, self.leaf_valid, index=self.leaf_index,
-                                       count=self.leaf_count)
+                pi, v = self.evaluator(self.leaf_state, self.leaf_mask, self.leaf_valid, **how)
                 cur.wait_stream(side)
                 _lib.check(self.L.spl_mcts_backup_kind(self.h, _ptr(self.leaf_mask), _ptr(pi), _ptr(v), 1 | dg, s),
                            "spl_mcts_backup_kind")
                 return
-            pi, v = self.evaluator(self.leaf_state, self.leaf_mask, self.leaf_valid, index=self.leaf_index,
-                                   count=self.leaf_count)
+            pi, v = self.evaluator(self.leaf_state, self.leaf_mask, self.leaf_valid, **how)
         else:
             _lib.check(self.L.spl_mcts_select(self.h, _ptr(self.leaf_state), _ptr(self.leaf_mask),
                                               _ptr(self.leaf_valid), s), "spl_mcts_select")

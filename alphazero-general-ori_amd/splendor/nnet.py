@@ -352,15 +352,22 @@ class FusedNet:
         self.mode = precision_mode(precision)
         self.w = pack_weights(FoldedNet(net).to(self.device).eval(), n_players)
 
-    def __call__(self, leaf_state, leaf_mask, pi=None, v=None, index=None, count=None):
+    staged = True    # takes a staged leaf buffer (spl_nn_forward_staged), every precision
+
+    def __call__(self, leaf_state, leaf_mask, pi=None, v=None, index=None, count=None, stage=None):
         """index / count (device int32, spl_mcts_select_compact's segmented list: B entries and
         ceil(B / 64) segment counts): evaluate only the listed rows (other rows of pi / v are
-        left as they are)."""
+        left as they are). stage (device bytes, new_stage: filled by spl_mcts_select_staged or
+        spl_nn_stage_leaves for these B rows): the same rows, read from the staged buffer —
+        leaf_state / leaf_mask are then not read."""
         B = leaf_state.shape[0]
         pi = pi if pi is not None else torch.empty((B, ACTIONS), dtype=torch.float32, device=self.device)
         v = v if v is not None else torch.empty((B, self.n), dtype=torch.float32, device=self.device)
         s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if self.mode:
+        if stage is not None:
+            _lib.check(_lib.lib().spl_nn_forward_staged(self.n, B, _ptr(stage), _ptr(self.w), _ptr(pi), _ptr(v),
+                                                        self.mode, s), "spl_nn_forward_staged")
+        elif self.mode:
             _lib.check(_lib.lib().spl_nn_forward_mode(self.n, B, _ptr(leaf_state), _ptr(leaf_mask), _ptr(index),
                                                       _ptr(count), _ptr(self.w), _ptr(pi), _ptr(v), self.mode, s),
                        "spl_nn_forward_mode")
@@ -372,6 +379,15 @@ class FusedNet:
                                                          _ptr(count), _ptr(self.w), _ptr(pi), _ptr(v), s),
                        "spl_nn_forward_indexed")
         return pi, v
+
+
+def new_stage(n_players, B, device):
+    """The staged leaf buffer for B trees (spl_nn_stage_bytes; layout in include/splendor_amd.h):
+    device bytes, zero-filled once here and never again."""
+    nbytes = int(_lib.lib().spl_nn_stage_bytes(n_players, B))
+    if nbytes < 0:
+        raise _lib.EngineError(f"spl_nn_stage_bytes({n_players}, {B}): invalid argument")
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
 
 
 def random_net(n_players=2, seed=0, device="cuda"):
@@ -427,10 +443,16 @@ class LeafEvaluator:
         """The fused kernel can evaluate a compacted leaf list (spl_nn_forward_indexed)."""
         return self.fused is not None
 
+    @property
+    def staged(self):
+        """The fused kernel can read the search's staged leaf buffer (spl_nn_forward_staged):
+        the NN leaves alone, like `indexed`."""
+        return self.fused is not None and self.indexed
+
     @torch.no_grad()
-    def __call__(self, leaf_state, leaf_mask, leaf_valid=None, index=None, count=None):
+    def __call__(self, leaf_state, leaf_mask, leaf_valid=None, index=None, count=None, stage=None):
         if self.fused is not None:
-            return self.fused(leaf_state, leaf_mask, self.pi_buf, self.v_buf, index=index, count=count)
+            return self.fused(leaf_state, leaf_mask, self.pi_buf, self.v_buf, index=index, count=count, stage=stage)
         if not self.use_graph:
             return self._run(leaf_state, leaf_mask)
         key = (leaf_state.data_ptr(), leaf_mask.data_ptr())

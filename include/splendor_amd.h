@@ -464,6 +464,46 @@ int spl_nn_forward_mode(int n_players, int B, const int8_t *leaf_state, const ui
                         const float *packed_weights, float *pi, float *v, int precision,
                         void *hip_stream);
 
+/* ---- staged leaves: the mask kernel hands the network its tiles ----
+ * The mask kernel that runs before the network has every leaf board on chip and knows which
+ * leaves need the network; with a staged leaf buffer it writes them where the network kernel
+ * wants them — list order, 32-leaf tiles, each tile already the int8 image the kernel keeps in
+ * LDS — so a network tile starts with one round of contiguous 16-byte loads instead of a scan
+ * of the segment counts, two dependent index hops and a byte scatter.
+ *
+ * The buffer: spl_nn_stage_bytes(n_players, B) bytes of device memory, 16-byte aligned,
+ * allocated and ZERO-FILLED ONCE by the caller (never again: the fill only gives the bytes the
+ * kernels never write a defined value). Layout (byte offsets; a16(x) = x rounded up to 16):
+ *     0                       i32   total: the number of listed leaves; 12 bytes reserved
+ *     16                      i32   rows[B]: the tree row of list entry p
+ *     M = a16(16 + 4 B)       u64   mask[B][7]: the legality masks in list order
+ *     X = a16(M + 56 B)       i8    x[ceil(B / 32)][7][32][X0S]: tile p / 32, slot p % 32 holds
+ *                                   entry p's board transposed, x[.][c][p % 32][r] = board[r][c],
+ *                                   X0S = R rounded up to 8, plus 4 if that is an even number of
+ *                                   dwords (60 / 76 / 92 for 2 / 3 / 4 players)
+ * The list is spl_mcts_select_compact's: segments of 64 trees in order, trees ascending inside
+ * a segment. Entries at and past `total` (rows, masks, tile slots) keep what they last held;
+ * the network kernel neither stores results for them nor lets them reach a result (bytes r >= R of
+ * a slot stay zero and meet zero weights). Returns the size or SPL_EINVAL. */
+long long spl_nn_stage_bytes(int n_players, int B);
+/* spl_mcts_select whose mask kernel also fills `stage` (leaf_mask by tree row, leaf_state and
+ * leaf_valid are written exactly as by spl_mcts_select). leaf_valid must be 16-byte aligned:
+ * every 64-tree segment counts the listed leaves of the segments before it from those bytes. */
+int spl_mcts_select_staged(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, uint8_t *leaf_valid,
+                           void *stage, void *hip_stream);
+/* The same mask-and-stage kernel on caller-supplied canonical boards without a tree: for the B
+ * boards of leaf_state, the rows with leaf_valid[b] != 0 get their mask (leaf_mask[b], under
+ * the context's token limit and rules) and are staged. B == 0 launches nothing. */
+int spl_nn_stage_leaves(const spl_ctx *ctx, int B, const int8_t *leaf_state, const uint8_t *leaf_valid,
+                        uint64_t *leaf_mask, void *stage, void *hip_stream);
+/* The network on the staged leaves: pi / v rows rows[p] for p < total are written, all others
+ * left untouched; bit-identical to spl_nn_forward_mode on the same list. B = the number of
+ * trees the buffer was sized and filled for. precision as spl_nn_forward_mode.
+ * All three: NULL or misaligned arguments (stage, leaf_valid, packed_weights: 16 bytes), or a
+ * precision outside 0 .. 2, return SPL_EINVAL before any launch. */
+int spl_nn_forward_staged(int n_players, int B, const void *stage, const float *packed_weights,
+                          float *pi, float *v, int precision, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
