@@ -13,6 +13,12 @@
 // The move loop is bounded by max_steps and touches no HBM; a task that has ended (or whose
 // row is inactive) is predicated off, every wave reaches every barrier, and the workgroup
 // leaves the loop when none of its tasks is live.
+//
+// spl_playout_seq runs the same kernel with the stream base read from a device counter (SEQ:
+// step0 = (*call_seq mod 2^23) 256, so a captured launch draws new streams at every replay)
+// and, given the search's NN-leaf list (LIST), on the listed rows only: a workgroup then owns
+// 64 / P consecutive list entries, found by a scan of the segment counts, and one past the
+// end of the list leaves before it stages anything. Task keys stay tied to the row.
 #include <hip/hip_runtime.h>
 
 #include "../../include/splendor_amd.h"
@@ -50,13 +56,79 @@ struct TableRegs {
     }
 };
 
-template <int N>
+// The leaf list as spl_mcts_select_compact writes it: segment j (rows 64 j .. 64 j + 63) has
+// count[j] entries at leaf_index[64 j ..]; the list is their concatenation in segment order.
+// Wave-collective, registers only unless `slot` is given: returns the list's length, and with
+// slot / offv (PT ints each, the calling wave's own) lane i gets the leaf_index position of list
+// entry e0 + i in `pos` (meaningful for entries below the length). A lane holds 4 consecutive
+// segments' counts and one DPP scan gives every segment's first entry, 256 segments per pass;
+// each segment that reaches into [e0, e0 + PT) marks the slot where it starts (and 64 j - start
+// in offv), and a prefix maximum over the slots gives every slot its segment (the scan of
+// nn_list_rows, nnet.hip, on plain 4-byte loads: the counts need no alignment here).
+__device__ __forceinline__ int list_rows(const int32_t *__restrict__ count, int nseg, int e0, int *slot, int *offv,
+                                         int &pos) {
+    const int lane = lane_id();
+    if (slot) slot[lane] = -1;
+    int base = 0;
+    for (int c0 = 0; c0 < nseg; c0 += 4 * 64) {
+        const int j0 = c0 + 4 * lane;
+        int v[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = min(max(count[min(j0 + q, nseg - 1)], 0), j0 + q < nseg ? 64 : 0);
+        const int own = v[0] + v[1] + v[2] + v[3];
+        // inclusive scan of the lanes' sums on DPP: row_shr 1 / 2 / 4 / 8 inside each 16-lane
+        // row (lanes without a source add 0), then row_bcast 15 (rows 1, 3) and 31 (rows 2, 3)
+        int inc = own;
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);
+        if (slot) {
+            int ex = base + inc - own;                   // first list entry of segment j0
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                if (v[q] > 0 && ex + v[q] > e0 && ex < e0 + PT) {
+                    const int sl = max(ex - e0, 0);
+                    slot[sl] = sl;
+                    offv[sl] = 64 * (j0 + q) - ex;
+                }
+                ex += v[q];
+            }
+        }
+        base += __builtin_amdgcn_readlane(inc, 63);
+    }
+    pos = 0;
+    if (slot) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        int f = slot[lane];                              // prefix maximum over slots 0 .. 63
+        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x111, 0xf, 0xf, false));
+        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x112, 0xf, 0xf, false));
+        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x114, 0xf, 0xf, false));
+        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x118, 0xf, 0xf, false));
+        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x142, 0xa, 0xf, false));
+        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x143, 0xc, 0xf, false));
+        if (f >= 0) pos = e0 + lane + offv[f];
+    }
+    return base;
+}
+
+// SEQ: the stream base is (*call_seq mod 2^23) SPL_PLAYOUT_SEQ_STREAMS instead of step0 (spl_playout_seq).
+// LIST (with SEQ): the rows are the entries of the leaf list; r0 / nr / nb then count list entries
+// and erow[] holds each entry's row (-1: an index outside 0 .. B - 1, which runs nothing).
+template <int N, bool SEQ, bool LIST>
 __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t *__restrict__ state,
                                                      const int8_t *__restrict__ player,
                                                      const uint8_t *__restrict__ active, int lim, int policy,
                                                      int max_steps, uint64_t seed, uint32_t step0, uint32_t bbase,
                                                      float *__restrict__ result, float *__restrict__ pi_out,
-                                                     int32_t *__restrict__ steps_out, int32_t *unfinished) {
+                                                     int32_t *__restrict__ steps_out, int32_t *unfinished,
+                                                     const int32_t *__restrict__ leaf_index,
+                                                     const int32_t *__restrict__ leaf_count,
+                                                     const uint32_t *__restrict__ call_seq) {
+    static_assert(SEQ || !LIST, "the list entry reads its stream base on the device");
     using Lx = Lay<N>;
     using Cv = Conv<N>;
     constexpr int ST = RolloutLds<N>::STRIDE;
@@ -77,11 +149,23 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
     __shared__ uint64_t pf0[WAVES][PT], pf1[PT];
     __shared__ uint32_t pcond[PT];
     __shared__ uint8_t pbad[WAVES][PT];
-    const int rpw = PT / P;                                  // rows per workgroup
-    const int r0 = blockIdx.x * rpw, nr = min(rpw, B - r0), nb = nr * P;
+    __shared__ int erow[LIST ? PT : 1], eoff[LIST ? PT : 1];
+    const int rpw = PT / P;                                  // rows (LIST: list entries) per workgroup
     const int tid = threadIdx.x, w = tid >> 6, l = lane_id();
+    const int r0 = blockIdx.x * rpw;
+    int nr = min(rpw, B - r0), lpos = 0;
+    if constexpr (LIST) {
+        // every wave scans the counts in registers, so the exit is block-uniform with no barrier
+        // before it; wave 0 also resolves the workgroup's entries
+        const int total = list_rows(leaf_count, (B + 63) >> 6, r0, w == 0 ? erow : nullptr, w == 0 ? eoff : nullptr,
+                                    lpos);
+        if (r0 >= total) return;
+        nr = min(rpw, total - r0);
+    }
+    const int nb = nr * P;
     const int lrow = l / P;                                  // task l = playout l - lrow * P of row r0 + lrow
-    const uint32_t board = bbase + (uint32_t)(r0 + lrow) * (uint32_t)P + (uint32_t)(l - lrow * P);
+    uint32_t board = bbase + (uint32_t)(r0 + lrow) * (uint32_t)P + (uint32_t)(l - lrow * P);
+    if constexpr (SEQ) step0 = (*call_seq & 0x7FFFFFu) * (uint32_t)SPL_PLAYOUT_SEQ_STREAMS;
     // prologue: the table loads go out first, the boards load while they are in flight
     {
         TableRegs<double, 41 * 9> q_quot;
@@ -96,19 +180,28 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
         q_rsv.fetch(K_ACT_RSV, tid);
         q_fac.fetch(&K_MASK_FACTORS[0][0], tid);
         const double recip = K_RECIP[min(tid, 8)];
+        if constexpr (LIST) {
+            __builtin_amdgcn_wave_barrier();                 // (wave 0 has read its eoff[] above)
+            if (w == 0) {
+                int r = -1;
+                if (l < nr && lpos < B) r = leaf_index[lpos];
+                erow[l] = r >= 0 && r < B ? r : -1;
+            }
+            lds_sync();
+        }
         if (tid < PT) {
-            const bool on = tid < nb && (!active || active[r0 + lrow]);
+            const bool on = tid < nb && (LIST ? erow[lrow] >= 0 : !active || active[r0 + lrow]);
             act[tid] = on;
             live[tid] = on;
-            pl[tid] = on && player ? player[r0 + lrow] : (int8_t)0;
+            pl[tid] = !LIST && on && player ? player[r0 + lrow] : (int8_t)0;
             nstep[tid] = max_steps;
 #pragma unroll
             for (int i = 0; i < N; i++) outc[tid][i] = 0.f;
         }
         // every task gets its own copy of its row's board (the P reads of a row hit the cache)
         for (int i = tid; i < nb * Cv::UNITS; i += THREADS) {
-            const int t = i / Cv::UNITS, u = i - t * Cv::UNITS, r = r0 + t / P;
-            if (!active || active[r]) Cv::load(lds + t * ST, state + (size_t)r * Lx::S, u);
+            const int t = i / Cv::UNITS, u = i - t * Cv::UNITS, r = LIST ? erow[t / P] : r0 + t / P;
+            if (LIST ? r >= 0 : !active || active[r]) Cv::load(lds + t * ST, state + (size_t)r * Lx::S, u);
         }
         if (tid < 4) kcount[tid] = 0;
         q_quot.put(&tabs.quot[0][0], tid);
@@ -120,6 +213,8 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
         if (tid < 9) tabs.recip[tid] = recip;
     }
     lds_sync();
+    const int myrow = LIST ? erow[lrow] : r0 + lrow;         // (the key stays the row's, not the entry's)
+    if constexpr (LIST) board = bbase + (uint32_t)myrow * (uint32_t)P + (uint32_t)(l - lrow * P);
     for (int t = 0; t < max_steps; ++t) {
         const uint32_t step = step0 + (uint32_t)t;
         if (tid < 4) kcount[tid] = 0;                    // (last read in the previous move phase)
@@ -186,7 +281,7 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
 #pragma unroll
                 for (int k = 0; k < 7; k++) cnt += __popcll(msk[b][k]);
                 const float inv = 1.0f / (float)max(cnt, 1);
-                float *po = pi_out + (size_t)(r0 + b / P) * SPL_ACTIONS;
+                float *po = pi_out + (size_t)(LIST ? erow[b / P] : r0 + b / P) * SPL_ACTIONS;
                 for (int a = tid; a < SPL_ACTIONS; a += THREADS) {
                     const bool bit = cnt ? (msk[b][a >> 6] >> (a & 63)) & 1 : a == SPL_ACTIONS - 1;
                     po[a] = bit ? inv : 0.f;
@@ -274,18 +369,41 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
         if (act[rr * P]) {
             float sum = 0.f;
             for (int j = 0; j < P; j++) sum += outc[rr * P + j][i];
-            result[(size_t)(r0 + rr) * N + i] = sum / (float)P;
+            result[(size_t)(LIST ? erow[rr] : r0 + rr) * N + i] = sum / (float)P;
         }
     }
     if (w == 0) {
         const bool on = l < nb && act[l];
-        if (steps_out && on) steps_out[(size_t)r0 * P + l] = nstep[l];
+        if (steps_out && on) steps_out[LIST ? (size_t)myrow * P + (l - lrow * P) : (size_t)r0 * P + l] = nstep[l];
         const uint64_t open = __ballot(l < nb && live[l]);   // still playing after max_steps moves
         if (unfinished && open && l == 0) atomicAdd(unfinished, (int32_t)__popcll(open));
     }
 }
 
 inline bool ok_ctx(const spl_ctx *c) { return c && c->n >= 2 && c->n <= 4; }
+
+// one launch of k_playout<N, SEQ, LIST>; a list launch is sized for B entries (the host cannot
+// know the list's length: the workgroups past its end leave at once)
+template <bool SEQ, bool LIST>
+int launch_playout(const spl_ctx *c, int B, const int8_t *state, const int8_t *player, const uint8_t *active,
+                   int policy, int playouts, int max_steps, uint64_t seed, uint32_t step0, uint32_t board_base,
+                   float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished, const int32_t *leaf_index,
+                   const int32_t *leaf_count, const uint32_t *call_seq, void *hs) {
+    const int rpw = PT / playouts;
+    const dim3 grid((unsigned)(((long long)B + rpw - 1) / rpw));
+#define SPL_PLAYOUT_LAUNCH(NP)                                                                            \
+    hipLaunchKernelGGL((k_playout<NP, SEQ, LIST>), grid, dim3(THREADS), 0, (hipStream_t)hs, B, playouts,  \
+                       state, player, active, pack_lim(c->token_limit, c->rules), policy, max_steps,      \
+                       seed, step0, board_base, result, pi_out, steps_out, unfinished, leaf_index,        \
+                       leaf_count, call_seq)
+    switch (c->n) {
+        case 2: SPL_PLAYOUT_LAUNCH(2); break;
+        case 3: SPL_PLAYOUT_LAUNCH(3); break;
+        default: SPL_PLAYOUT_LAUNCH(4); break;
+    }
+#undef SPL_PLAYOUT_LAUNCH
+    return hipGetLastError() == hipSuccess ? 0 : SPL_EDEVICE;
+}
 
 }  // namespace
 
@@ -298,17 +416,25 @@ extern "C" int spl_playout(const spl_ctx *c, int B, const int8_t *state, const i
         (uint64_t)step0 + (uint64_t)max_steps > 0x80000000ull)
         return SPL_EINVAL;
     if (!B) return 0;
-    const int rpw = PT / playouts;
-    const dim3 grid((unsigned)(((long long)B + rpw - 1) / rpw));
-#define SPL_PLAYOUT_LAUNCH(NP)                                                                          \
-    hipLaunchKernelGGL(k_playout<NP>, grid, dim3(THREADS), 0, (hipStream_t)hs, B, playouts, state,      \
-                       player, active, pack_lim(c->token_limit, c->rules), policy, max_steps, seed,     \
-                       step0, board_base, result, pi_out, steps_out, unfinished)
-    switch (c->n) {
-        case 2: SPL_PLAYOUT_LAUNCH(2); break;
-        case 3: SPL_PLAYOUT_LAUNCH(3); break;
-        default: SPL_PLAYOUT_LAUNCH(4); break;
-    }
-#undef SPL_PLAYOUT_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : SPL_EDEVICE;
+    return launch_playout<false, false>(c, B, state, player, active, policy, playouts, max_steps, seed, step0,
+                                        board_base, result, pi_out, steps_out, unfinished, nullptr, nullptr, nullptr,
+                                        hs);
+}
+
+extern "C" int spl_playout_seq(const spl_ctx *c, int B, const int8_t *state, const uint8_t *active,
+                               const int32_t *leaf_index, const int32_t *leaf_count, int policy, int playouts,
+                               int max_steps, uint64_t seed, const uint32_t *call_seq, uint32_t board_base,
+                               float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished, void *hs) {
+    if (!ok_ctx(c) || !state || !result || !call_seq || B < 0 || policy < SPL_PLAYOUT_UNIFORM ||
+        policy > SPL_PLAYOUT_BUY_FIRST || playouts < 1 || playouts > 64 || max_steps < 1 ||
+        max_steps > SPL_PLAYOUT_SEQ_STREAMS || !leaf_index != !leaf_count || (active && leaf_index))
+        return SPL_EINVAL;
+    if (!B) return 0;
+    if (leaf_index)
+        return launch_playout<true, true>(c, B, state, nullptr, nullptr, policy, playouts, max_steps, seed, 0,
+                                          board_base, result, pi_out, steps_out, unfinished, leaf_index, leaf_count,
+                                          call_seq, hs);
+    return launch_playout<true, false>(c, B, state, nullptr, active, policy, playouts, max_steps, seed, 0,
+                                       board_base, result, pi_out, steps_out, unfinished, nullptr, nullptr, call_seq,
+                                       hs);
 }

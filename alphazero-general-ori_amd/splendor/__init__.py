@@ -5,6 +5,7 @@ Modules:
   env           batched device-resident environment (SplendorEngine, RolloutBatch)
   SplendorGame  the reference's Game interface (SplendorGame.py:11-86), engine-backed
   SplendorPlayers  RandomPlayer / GreedyPlayer for the sequential Arena (one-board kernel calls)
-  playout       PlayoutEvaluator: leaf values from random playouts (network-free search players)
+  playout       PlayoutEvaluator: leaf values from random playouts (network-free search players
+                and the rollout bootstrap of Coach.learn), safe under graph capture
   arena, pit    BatchedArena (the Coach's gate) and BatchedPit (any two player kinds), on device
 """

@@ -11,7 +11,12 @@ the same examples as a columnar `ExampleSet` and appends it to `trainExamplesHis
 variants are produced when training batches are assembled. `learn()`
 is Coach.learn (Coach.py:102-164): self-play iterations, training on the example history,
 the new-vs-previous BatchedArena gate and checkpoints. `args.selfplay_reserve = False` makes
-the self-play games reserve-free while the gate plays the full game.
+the self-play games reserve-free while the gate plays the full game. `args.bootstrap_iters = k`
+plays the self-play of learn()'s first k iterations with the network-free rollout search
+(splendor.playout.PlayoutEvaluator on the same trees: uniform priors, leaf values from
+`args.bootstrap_playouts` random playouts under `args.bootstrap_policy`), the usual cold start
+from a random-init network; `use_rollout_selfplay()` is the same switch for callers that drive
+executeIteration themselves and `refresh_network()` the way back.
 """
 import numpy as np
 import torch
@@ -20,6 +25,7 @@ from . import _lib
 from .env import unpack_mask
 from .arena import BatchedArena, accept_new_network
 from .examples import ExampleHistory, ExampleSet, LazySymmetryExamples
+from .playout import PlayoutEvaluator
 from .search import evaluator_for, nn_precision_arg
 from .selfplay import SelfPlay, gather_examples
 
@@ -51,12 +57,16 @@ class Coach:
         args.selfplay_reserve (default True): False plays self-play without the reserve moves
         12..26 (SplendorGame.disableReserve for the self-play handle only, the reference's
         training recipe, SplendorLogicNumba.py:96); the recorded valids and pi are the
-        reserve-free tree's. The engine's rules are the same before and after."""
+        reserve-free tree's. The engine's rules are the same before and after.
+        args.bootstrap_iters (default 0: nothing changes anywhere), args.bootstrap_playouts
+        (default 4) and args.bootstrap_policy (default "buy_first"): learn()'s first iterations
+        play their self-play with the rollout search (use_rollout_selfplay)."""
         self.game, self.nnet, self.args = game, nnet, args
         B = int(batch or _arg(args, "numEps", 1))
         self.B = B
-        self.seed = seed
+        self.seed, self.board_base = seed, board_base
         self.mem_budget = mem_budget
+        self._rollout_ev = {}                                # (playouts, policy) -> PlayoutEvaluator
         # args.selfplay_reserve = False: the self-play handle alone is reserve-free (the engine's
         # own rules are put back once it exists); the gate, the pit and check_valid play the
         # full game on the same engine: the reference's "train without, validate with"
@@ -132,8 +142,26 @@ class Coach:
     def refresh_network(self):
         """Re-pack the leaf evaluator after the network's weights changed (the fused kernel
         reads a packed copy)."""
-        self.sp.evaluator = evaluator_for(self.game.engine, self.nnet, self.B,
-                                          precision=nn_precision_arg(self.args))
+        self.sp.set_evaluator(evaluator_for(self.game.engine, self.nnet, self.B,
+                                            precision=nn_precision_arg(self.args)))
+
+    def use_rollout_selfplay(self, playouts=None, policy=None):
+        """Play the following self-play on the same trees with the network-free rollout search:
+        the handle's evaluator becomes a PlayoutEvaluator (playouts per leaf and playout policy
+        default to args.bootstrap_playouts / args.bootstrap_policy, 4 buy-first) on the Coach's
+        seed and board_base and the handle's rules. The handle's simulations, cpuct, fpu, noise
+        and temperature apply unchanged and the examples are recorded as always. One evaluator
+        per (playouts, policy) lives as long as the Coach, so its call counter, and with it its
+        Philox streams, keep advancing across iterations. refresh_network() puts the network
+        evaluator back. Returns the evaluator."""
+        P = int(playouts if playouts is not None else _arg(self.args, "bootstrap_playouts", 4) or 4)
+        policy = policy or _arg(self.args, "bootstrap_policy", "buy_first") or "buy_first"
+        ev = self._rollout_ev.get((P, policy))
+        if ev is None:
+            ev = self._rollout_ev[P, policy] = PlayoutEvaluator(self.game.engine, P, policy, seed=self.seed,
+                                                                board_base=self.board_base, rules=self.sp.rules)
+        self.sp.set_evaluator(ev)
+        return ev
 
     def learn(self, pnet=None, log=None):
         """Coach.learn (Coach.py:102-164): for numIters iterations, numEps self-play games
@@ -143,14 +171,19 @@ class Coach:
         kept iff it wins >= updateThreshold of the decisive games (under torch.distributed
         every rank's examples are all-gathered first, so all ranks train on the same set);
         checkpoints as
-        checkpoint_<i>.pt / best.pt / temp.pt in args.checkpoint. Returns per-iteration
-        (nwins, pwins, draws, accepted)."""
+        checkpoint_<i>.pt / best.pt / temp.pt in args.checkpoint. In iterations i <=
+        args.bootstrap_iters the self-play runs on the rollout search (use_rollout_selfplay);
+        training, the gate and the checkpoints are the same, and the network evaluator is back
+        after the iteration. Returns per-iteration (nwins, pwins, draws, accepted)."""
         from .NNet import NNetWrapper
         folder = _arg(self.args, "checkpoint", "checkpoint")
         pnet = pnet or NNetWrapper(self.game, dict(self.nnet.args), device=self.nnet.device)
         history = []
+        bootstrap = int(_arg(self.args, "bootstrap_iters", 0) or 0)
         for i in range(1, int(_arg(self.args, "numIters", 1)) + 1):
             if not _arg(self.args, "skipFirstSelfPlay", False) or i > 1:
+                if i <= bootstrap:
+                    self.use_rollout_selfplay()
                 self.sp.reset()
                 self.executeIteration(int(_arg(self.args, "numEps", self.B)), gather=True)
             self.saveTrainExamples(folder)

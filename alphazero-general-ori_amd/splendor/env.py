@@ -290,6 +290,43 @@ class SplendorEngine:
                    "spl_playout")
         return out
 
+    def playout_seq(self, state, call_seq, active=None, index=None, count=None, policy="buy_first", playouts=1,
+                    max_steps=None, seed=0, board_base=0, pi=False, steps=False, out=None):
+        """playout() for the search's leaves, safe to capture in a graph (spl_playout_seq): the
+        boards are canonical (mover = seat 0) and the stream base is read on the device, step0 =
+        (call_seq[0] mod 2^23) 256 with call_seq a one-element device tensor of 4-byte integers
+        that the launch only reads (the caller advances it on the stream). The rows that run:
+        the leaf list index / count (int32 [B] / [ceil(B / 64)], as spl_mcts_select_compact
+        writes it) if given, else the rows with active[b] != 0, else all; every other row keeps
+        its entries of every output. Results, bit for bit, as playout(active = those rows,
+        step0 = that base). max_steps is at most 256."""
+        B, P, dev = state.shape[0], int(playouts), self.device
+        kind = self.PLAYOUT_POLICIES.get(policy, policy)
+        if not isinstance(kind, int):
+            raise ValueError(f"playout_seq: policy must be one of {sorted(self.PLAYOUT_POLICIES)}, got {policy!r}")
+        for t, dt, rows, name in ((state, (torch.int8,), B, "state"), (active, (torch.uint8,), B, "active"),
+                                  (index, (torch.int32,), B, "index"), (count, (torch.int32,), (B + 63) // 64, "count"),
+                                  (call_seq, (torch.int32, torch.uint32), 1, "call_seq")):
+            if t is not None and (t.dtype not in dt or t.shape[0] != rows or not t.is_contiguous()):
+                raise ValueError(f"playout_seq: {name} must be a contiguous {dt[0]} tensor with {rows} rows")
+        if call_seq is None or (index is None) != (count is None) or (active is not None and index is not None):
+            raise ValueError("playout_seq: call_seq is required; index and count go together and exclude active")
+        out = dict(out) if out is not None else {}
+        if "result" not in out:
+            out["result"] = torch.zeros((B, self.n), dtype=torch.float32, device=dev)
+        if pi and "pi" not in out:
+            out["pi"] = torch.zeros((B, ACTIONS), dtype=torch.float32, device=dev)
+        if steps and "steps" not in out:
+            out["steps"] = torch.zeros((B, P), dtype=torch.int32, device=dev)
+        if "unfinished" not in out:                              # (a reused counter keeps adding up)
+            out["unfinished"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(self.L.spl_playout_seq(self.ctx, B, _ptr(state), _ptr(active), _ptr(index), _ptr(count), kind, P,
+                                          int(62 * self.n if max_steps is None else max_steps), seed, _ptr(call_seq),
+                                          int(board_base), _ptr(out["result"]), _ptr(out["pi"]) if pi else None,
+                                          _ptr(out["steps"]) if steps else None, _ptr(out["unfinished"]), self._s()),
+                   "spl_playout_seq")
+        return out
+
 
 class RolloutBatch:
     """B boards of random-policy self-play, stepped by one fused launch per step

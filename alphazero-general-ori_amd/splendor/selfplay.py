@@ -42,6 +42,14 @@ class SelfPlay(BatchedMCTS):
 
     GRAPH_ITERS = 8
 
+    def set_evaluator(self, evaluator):
+        """Replace the leaf evaluator between iterations. The captured graphs hold the old
+        evaluator's launches and buffers, so they are dropped; the next graphed run captures
+        again."""
+        self.evaluator = evaluator
+        self.graph = None
+        self.graph_k = None
+
     def run(self, k, use_graph=True):
         """k iterations. With use_graph, replays of a graph of GRAPH_ITERS iterations (a graph
         launch leaves ~9 us of idle GPU before the next one, measured; one per 8 iterations

@@ -59,7 +59,7 @@ int spl_ctx_set_token_limit(spl_ctx *ctx, int token_limit);
  * and make_move, scores, end checks, chance and symmetries are unchanged. The mask under the
  * rule is therefore the full mask with bits 12..26 cleared, then bit 408 set iff bits 0..407
  * are empty. Every call that builds a legality mask from the context honours the flags at
- * launch time: spl_valid_moves, spl_player_move, spl_rollout_step / _run, spl_playout.
+ * launch time: spl_valid_moves, spl_player_move, spl_rollout_step / _run, spl_playout / _seq.
  * A search handle copies the context's rules (as its token limit) in spl_mcts_create and keeps
  * them for its lifetime: trees store masks, so later changes of the context do not reach it.
  * set_rules: SPL_EINVAL on a NULL context or unknown bits (nothing is changed); the token limit
@@ -229,6 +229,38 @@ int spl_playout(const spl_ctx *ctx, int B, const int8_t *state, const int8_t *pl
                 float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished,
                 void *hip_stream);
 
+/* spl_playout for the search's leaves, safe to capture in a graph: the stream base is read on
+ * the device, and the rows may be given as the NN-leaf list. The rows are canonical boards whose
+ * mover is seat 0 (spl_playout with player == NULL). Which rows run:
+ *   leaf_index and leaf_count both given: the segmented list exactly as spl_mcts_select_compact
+ *     writes it and spl_nn_forward_indexed reads it: ceil(B / 64) counts, segment j's entries at
+ *     leaf_index[64 j .. 64 j + leaf_count[j]), in any order inside a segment (the counts need no
+ *     alignment; a count is read clamped to 0..64 and an entry outside 0..B-1 runs nothing);
+ *   else active given: the rows with active[b] != 0;  else: every row.
+ * call_seq is one device u32 that the kernel only reads: with c = *call_seq when the kernel
+ * runs, the stream base is step0 = (c mod 2^23) SPL_PLAYOUT_SEQ_STREAMS. The caller advances the
+ * counter (a stream-ordered add is an ordinary captured operation), so every replay of a
+ * captured launch draws new streams. max_steps is limited to 1..SPL_PLAYOUT_SEQ_STREAMS, so
+ * consecutive calls' streams never overlap and step0 + max_steps <= 0x80000000 always holds.
+ * For every row b that runs, result, pi_out and steps_out equal, bit for bit, those of
+ * spl_playout(player = NULL, active = exactly those rows, step0 as above): task keys stay tied
+ * to the row, not to the list position (playout j of row b draws from Philox board id
+ * board_base + b P + j), and the row's result is the f32 sum in ascending j over (float)P. Rows
+ * that do not run keep every output byte; *unfinished accumulates as in spl_playout.
+ * With a list a workgroup owns 64 / P consecutive list entries; the grid is sized for B
+ * entries, every workgroup finds its entries from a scan of the segment counts, and one past
+ * the end of the list leaves before it stages anything. SPL_EINVAL before any launch: NULL ctx /
+ * state / result / call_seq, active together with a list, exactly one of leaf_index /
+ * leaf_count NULL, B < 0, policy outside 0..1, playouts outside 1..64, max_steps outside
+ * 1..256. B == 0 launches nothing. */
+#define SPL_PLAYOUT_SEQ_STREAMS 256
+int spl_playout_seq(const spl_ctx *ctx, int B, const int8_t *state, const uint8_t *active,
+                    const int32_t *leaf_index, const int32_t *leaf_count,
+                    int policy, int playouts, int max_steps, uint64_t seed,
+                    const uint32_t *call_seq, uint32_t board_base,
+                    float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished,
+                    void *hip_stream);
+
 
 /* ===================================================================== MCTS
  * Device-resident batched PUCT search (MCTS.py), one tree per board/game, B trees.
@@ -307,8 +339,8 @@ int spl_mcts_select(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, uint8_
  * segment j = trees 64 j .. 64 j + 63; leaf_count (device, ceil(B / 64) i32, 16-byte aligned)
  * holds each segment's number of such trees and leaf_index (device, B i32) their ids at
  * leaf_index[64 j .. 64 j + leaf_count[j]) in no particular order; the list is the segments'
- * entries in segment order. Pair with spl_nn_forward_indexed so the network runs on those
- * leaves only (terminal leaves and idle trees need no evaluation: ~30 % of all trees per
+ * entries in segment order. Pair with spl_nn_forward_indexed (or spl_playout_seq) so the
+ * network (the playouts) runs on those leaves only (terminal leaves and idle trees need no evaluation: ~30 % of all trees per
  * iteration at BASELINE config 3's steady state). (ABI 10 kept one compact list and one count:
  * every 64-tree workgroup then took its place with a returning atomic on one counter.) */
 int spl_mcts_select_compact(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask, uint8_t *leaf_valid,

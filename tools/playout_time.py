@@ -10,6 +10,15 @@ launches after --warmup, the playouts' step-count distribution, and the rates in
 per second (moves actually played for the playout, B K for the rollout).
 
   python tools/playout_time.py [--players 2] [--boards 32768] [--reps 30] [--out profiles/playout.json]
+
+--mode list: spl_playout_seq on a leaf list against spl_playout(active=) on the same rows: a
+fixed seeded --share of the boards (default 0.69, config 3's NN-leaf share) is listed, segment
+by segment as spl_mcts_select_compact lists leaves; the two launches alternate in one process
+(buy-first playouts, --playouts per leaf), outputs compared bit for bit first.
+--mode iteration: ms per self-play iteration (select, playouts, backup, commit) of SelfPlay at
+--boards games with the rollout evaluator (--playouts, buy-first) at config 3's search
+arguments, eager and as replayed graphs, over --iters iterations after --stagger warm-up
+iterations, with the window's capacity events. Both print one JSON record and write it to --out.
 """
 import argparse
 import json
@@ -38,6 +47,83 @@ def summary(us):
             "p90_us": round(float(np.percentile(us, 90)), 1), "launches": int(len(us))}
 
 
+def list_mode(a):
+    from splendor.env import RolloutBatch, SplendorEngine
+    n, B, P = a.players, a.boards, a.playouts
+    e = SplendorEngine(n, device="cuda:0")
+    dev = e.device
+    rb = RolloutBatch(e, B, seed=a.seed)
+    moves = a.moves if a.moves is not None else 20 * n
+    rb.run(moves, masks=False)
+    st = e.canonical(rb.state, rb.player).contiguous()
+    listed = np.random.default_rng(a.seed).random(B) < a.share
+    nseg = (B + 63) // 64
+    index, count = np.zeros(B, np.int32), np.zeros(nseg, np.int32)
+    for j in range(nseg):
+        rows = np.flatnonzero(listed[64 * j:64 * j + 64]) + 64 * j
+        index[64 * j:64 * j + len(rows)] = rows
+        count[j] = len(rows)
+    flags = torch.from_numpy(listed.astype(np.uint8)).to(dev)
+    index, count = torch.from_numpy(index).to(dev), torch.from_numpy(count).to(dev)
+    seq = torch.tensor([5], dtype=torch.int32, device=dev)
+    kw = dict(policy="buy_first", playouts=P, seed=a.seed, pi=True)
+    o_flag = e.playout(st, active=flags, step0=5 * 256, **kw)
+    o_list = e.playout_seq(st, seq, index=index, count=count, **kw)
+    o_seqf = e.playout_seq(st, seq, active=flags, **kw)
+    torch.cuda.synchronize()
+    for o in (o_list, o_seqf):
+        assert torch.equal(o["result"], o_flag["result"]) and torch.equal(o["pi"], o_flag["pi"])
+    runs = {"playout_flags": lambda: e.playout(st, active=flags, step0=5 * 256, out=o_flag, **kw),
+            "playout_seq_list": lambda: e.playout_seq(st, seq, index=index, count=count, out=o_list, **kw),
+            "playout_seq_flags": lambda: e.playout_seq(st, seq, active=flags, out=o_seqf, **kw)}
+    times = {k: [] for k in runs}
+    for rep in range(a.warmup + a.reps):
+        for k, fn in runs.items():
+            t = timed(fn)
+            if rep >= a.warmup:
+                times[k].append(t)
+    rec = {"mode": "list", "players": n, "boards": B, "playouts": P, "policy": "buy_first", "moves_from_deal": moves,
+           "seed": a.seed, "share": a.share, "listed": int(listed.sum()), "outputs_bit_identical": True}
+    rec.update({k: summary(v) for k, v in times.items()})
+    rec["list_over_flags"] = round(rec["playout_seq_list"]["median_us"] / rec["playout_flags"]["median_us"], 3)
+    return rec
+
+
+def iteration_mode(a):
+    import time
+    from splendor.env import SplendorEngine
+    from splendor.playout import PlayoutEvaluator
+    from splendor.selfplay import SelfPlay
+    n, B, P = a.players, a.boards, a.playouts
+    e = SplendorEngine(n, device="cuda:0")
+    args = dict(numMCTSSims=100, cpuct=2.5, fpu=0.3, prob_fullMCTS=0.25, ratio_fullMCTS=5, forced_playouts=False,
+                dirichletAlpha=0.3, temperature=[1.25, 0.8], tempThreshold=10)
+    rec = {"mode": "iteration", "players": n, "games": B, "playouts": P, "policy": "buy_first", "args": args,
+           "stagger_iterations": a.stagger, "iterations": a.iters}
+    sp = SelfPlay(e, B, args, evaluator=PlayoutEvaluator(e, P, "buy_first", seed=a.seed), dirichlet_noise=True,
+                  seed=a.seed)
+    sp.reset()
+    sp.run(a.stagger, use_graph=True)
+    sp.drain(allow_drops=True)
+    for name, graph in (("graphed", True), ("eager", False)):
+        torch.cuda.synchronize()
+        before = sp.counter_snapshot()
+        t0 = time.perf_counter()
+        done = 0
+        while done < a.iters:                                # (drained as a training run drains)
+            sp.run(min(256, a.iters - done), use_graph=graph)
+            done += 256
+            sp.drain(allow_drops=True)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        d = sp.counter_delta(before, sp.counter_snapshot())
+        rec[name] = {"ms_per_iteration": round(dt / a.iters * 1e3, 4), "simulations_per_s": d["sims_backed"] / dt,
+                     "moves": d["moves"], "games_done": d["games_done"],
+                     "capacity_events": {k: d[k] for k in ("prunes", "resets", "unexpanded")}}
+    rec["evaluator_calls"] = sp.evaluator.calls
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--players", type=int, default=2)
@@ -48,7 +134,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "playout.json"))
+    ap.add_argument("--mode", choices=("launch", "list", "iteration"), default="launch")
+    ap.add_argument("--share", type=float, default=0.69, help="list mode: share of the boards that is listed")
+    ap.add_argument("--iters", type=int, default=2000, help="iteration mode: timed iterations per variant")
+    ap.add_argument("--stagger", type=int, default=600, help="iteration mode: warm-up iterations")
     a = ap.parse_args()
+    if a.mode != "launch":
+        rec = (list_mode if a.mode == "list" else iteration_mode)(a)
+        print(json.dumps(rec, indent=1), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+            f.write("\n")
+        return
     from splendor.env import RolloutBatch, SplendorEngine
     n, B, P = a.players, a.boards, a.playouts
     e = SplendorEngine(n, device="cuda:0")

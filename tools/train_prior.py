@@ -6,12 +6,16 @@ concurrent trees, training on the example history (GenericNNetWrapper.train's lo
 schedule, larger batches), the BatchedArena gate against the previous weights. Writes the
 accepted weights as a plain state_dict checkpoint ({"state_dict": ...}, weights-only loadable)
 and one JSON line per iteration (losses, arena result, self-play figures) to stdout:
-    python3 tools/train_prior.py OUT.pt [iterations] [games] [no-reserve]
+    python3 tools/train_prior.py OUT.pt [iterations] [games] [no-reserve] [bootstrap=K[:P]]
 bench.py --net OUT.pt then runs the headline on these weights. A fourth argument `no-reserve`
 plays the self-play games without the reserve moves 12..26 (args.selfplay_reserve = False,
-the reference's training recipe); the arena gate still plays the full game."""
+the reference's training recipe); the arena gate still plays the full game. `bootstrap=K[:P]`
+(anywhere after OUT.pt) plays the self-play of the first K iterations with the network-free
+rollout search, P buy-first playouts per leaf (default 4; Coach.use_rollout_selfplay), on the
+same trees and search arguments; every iteration's line names the evaluator that played it."""
 import json
 import os
+import re
 import sys
 import time
 
@@ -24,6 +28,13 @@ from splendor.NNet import NNetWrapper  # noqa: E402
 from splendor.SplendorGame import SplendorGame  # noqa: E402
 from splendor.coach import Coach  # noqa: E402
 
+bootstrap_iters, bootstrap_playouts = 0, 4
+for arg in [x for x in sys.argv[1:] if x.startswith("bootstrap=")]:
+    m = re.fullmatch(r"bootstrap=(\d+)(?::(\d+))?", arg)
+    if not m:
+        raise SystemExit(f"{arg}: expected bootstrap=ITERATIONS[:PLAYOUTS]")
+    bootstrap_iters, bootstrap_playouts = int(m.group(1)), int(m.group(2) or 4)
+    sys.argv.remove(arg)
 out = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/trained_2p.pt"
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 games = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
@@ -56,13 +67,18 @@ pnet = NNetWrapper(g, dict(nn.args), device=nn.device)
 accepted = 0
 for i in range(1, iters + 1):
     t0 = time.perf_counter()
+    played = "network"
+    if i <= bootstrap_iters:                                # (learn() puts the network back afterwards)
+        ev = coach.use_rollout_selfplay(playouts=bootstrap_playouts)
+        played = f"rollout:{ev.policy}:{ev.playouts}"
     (nw, pw, dr, ok), = coach.learn(pnet=pnet)
     accepted += bool(ok)
     st = coach.sp.stats()
     print(json.dumps({"iteration": i, "seconds": time.perf_counter() - t0, "examples": last.get("examples"),
                       "losses": {k: float(v) for k, v in (last.get("losses") or {}).items()},
-                      "arena_new_prev_draws": [nw, pw, dr], "accepted": bool(ok),
+                      "arena_new_prev_draws": [nw, pw, dr], "accepted": bool(ok), "selfplay_evaluator": played,
                       "selfplay_leaf_depth_now": st["leaf_depth_now"]}), flush=True)
 os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
 torch.save({"state_dict": nn.nnet.state_dict(), "iterations": iters, "accepted": accepted}, out)
-print(json.dumps({"saved": out, "iterations": iters, "accepted": accepted}), flush=True)
+print(json.dumps({"saved": out, "iterations": iters, "accepted": accepted, "bootstrap_iters": bootstrap_iters,
+                  "bootstrap_playouts": bootstrap_playouts}), flush=True)
