@@ -10,8 +10,10 @@
 
 #include "../../include/splendor_amd.h"
 
+#include "board_phases.h"
 #include "mcts_device.h"
 #include "nn_stage.h"
+#include "spl_ctx.h"
 
 using namespace spl;
 
@@ -45,12 +47,6 @@ __device__ __noinline__ void bounds_note(int site, long long v, int t) {
     do {                            \
     } while (0)
 #endif
-
-struct spl_ctx {  // must match splendor_env.hip
-    int n;
-    int token_limit;
-    int rules;
-};
 
 struct spl_mcts {
     int n, B, S, token_limit;
@@ -2033,9 +2029,10 @@ __global__ __launch_bounds__(64) void k_select_lanes(Pools P, SearchCfg C, int B
 
 // ------------------------------------------------------------ leaf masks
 // getValidMoves(leaf, 0) (MCTS.py:136) for every NN leaf of a select, lane per leaf, 64
-// leaves per workgroup: the rollout kernel's factorised predicate and mask-word phases
-// (splendor_device.h lane_predicates_part / lane_mask_word_fast, exact path for boards
-// outside the fast domain), then the pass bit iff nothing else is legal (:263). Replaces
+// leaves per workgroup at the rollout kernel's LDS stride: its register-staged prologue and its
+// predicate and mask-word phases, called as they are (board_phases.h BoardRegs / StageRegs,
+// phase_predicates, phase_mask_words; player 0: the leaves are canonical), then the pass bit iff
+// nothing else is legal (:263). The kernel's own: the leaf list and the staged tiles. Replaces
 // the wave-per-board mask of the descent kernel (its lanes are idle for it anyway).
 // (Until late round 6 this kernel also filed the trees whose leaf was deep into the first
 // launch slots of the next select, behind one returning atomic per workgroup on a shared
@@ -2044,7 +2041,7 @@ __global__ __launch_bounds__(64) void k_select_lanes(Pools P, SearchCfg C, int B
 // select now takes tree = slot, A/B 0.4471 / 0.4462 vs 0.4486 / 0.4485 ms.)
 // leaf_index / leaf_count (optional): the NN leaves for the indexed network kernel, segment by
 // segment without atomics: segment j = this kernel's workgroup j (trees 64 j .. 64 j + 63) lists
-// its leaves at leaf_index[64 j ..] and their number at leaf_count[j] (nn_list_rows)
+// its leaves at leaf_index[64 j ..] and their number at leaf_count[j] (nn_stage.h leaf_list_scan)
 // per-workgroup timestamps of the last k_leaf_mask launch (diagnostic builds only,
 // -DLM_PROBE=1; never the product): s_memrealtime (100 MHz) at entry, after each of the three
 // barriers and at exit
@@ -2081,15 +2078,12 @@ __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, cons
                                                    int32_t *__restrict__ leaf_count,
                                                    char *__restrict__ stage) {
     using Lx = Lay<N>;
-    using Cv = Conv<N>;
-    constexpr int RB = 64, ST = (Lx::ROWS % 2 ? Lx::ROWS : Lx::ROWS + 1) * 8;
+    constexpr int RB = 64, ST = RolloutLds<N>::STRIDE;
     static_assert(Lx::ROWS == nnstage::rows(N) && 4 * ((Lx::ROWS + 3) / 4) <= nnstage::x0s(N) &&
                       nnstage::TILE == 32, "staged tile image (nn_stage.h)");
     __shared__ __align__(16) int8_t lds[RB * ST];
-    __shared__ uint64_t mfac[7 * 116];
-    __shared__ uint64_t pf0[4][RB], pf1[RB];
-    __shared__ uint32_t pcond[RB];
-    __shared__ uint8_t pbad[4][RB];
+    __shared__ uint64_t mfac[MASK_FACTOR_WORDS];
+    __shared__ PredLds<RB> pred;
     __shared__ uint64_t msk[RB][7];
     __shared__ int wsum[4];                              // (STG) the waves' counts of earlier leaves
     __shared__ int8_t lst[STG ? RB : 1], rnk[STG ? RB : 1];   // (STG) rank -> leaf, leaf -> rank / -1
@@ -2126,37 +2120,15 @@ __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, cons
     // the boards and the mask factors: every load issued before the first LDS store (a loop of
     // load -> store pairs waits one round trip per iteration — 17 of this kernel's 19 us at
     // config 3, LM_PROBE; now one)
-    constexpr int FW = (7 * 116 + 255) / 256;            // factor words per thread
-    uint64_t fw[FW];
-#pragma unroll
-    for (int k = 0; k < FW; k++) {
-        const int i = tid + 256 * k;
-        fw[k] = i < 7 * 116 ? (&K_MASK_FACTORS[0][0])[i] : 0;
+    {
+        const int8_t *const gst = leaf_state + (size_t)b0 * Lx::S;
+        StageRegs<uint64_t, MASK_FACTOR_WORDS, 256> q_fac;
+        BoardRegs<N, RB, 256> q_boards;
+        q_fac.fetch(&K_MASK_FACTORS[0][0], tid);
+        q_boards.fetch(gst, nb, tid);
+        q_boards.put(lds, gst, nb, tid);
+        q_fac.put(mfac, tid);
     }
-    if constexpr (Cv::QUAD) {
-        constexpr int BU = (RB * Cv::UNITS + 255) / 256;  // board units (4 rows) per thread
-        uint32_t d[BU][7];
-#pragma unroll
-        for (int k = 0; k < BU; k++) {
-            const int i = min(tid + 256 * k, nb * Cv::UNITS - 1), b = i / Cv::UNITS, u = i - b * Cv::UNITS;
-            const uint32_t *g = reinterpret_cast<const uint32_t *>(leaf_state + (size_t)(b0 + b) * Lx::S) + 7 * u;
-#pragma unroll
-            for (int q = 0; q < 7; q++) d[k][q] = g[q];
-        }
-#pragma unroll
-        for (int k = 0; k < BU; k++) {
-            const int i = tid + 256 * k, b = i / Cv::UNITS, u = i - b * Cv::UNITS;
-            if (i < nb * Cv::UNITS) quad_rows_put(d[k], reinterpret_cast<uint64_t *>(lds + b * ST) + 4 * u);
-        }
-    } else {
-        for (int i = tid; i < nb * Cv::UNITS; i += 256) {
-            const int b = i / Cv::UNITS, u = i - b * Cv::UNITS;
-            Cv::load(lds + b * ST, leaf_state + (size_t)(b0 + b) * Lx::S, u);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < FW; k++)
-        if (tid + 256 * k < 7 * 116) mfac[tid + 256 * k] = fw[k];
     if constexpr (STG) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
@@ -2216,49 +2188,10 @@ __global__ __launch_bounds__(256) void k_leaf_mask(Pools P, int B, int lim, cons
             reinterpret_cast<int32_t *>(stage + nnstage::ROWS_OFF)[base + rank] = b0 + l;
         if (blockIdx.x == gridDim.x - 1 && tid == 0) *reinterpret_cast<int32_t *>(stage) = base + nlist;
     }
-    if (l < nb) {                                        // predicates: part w of every leaf
-        uint64_t f0, f1;
-        uint32_t cc;
-        bool bad;
-        const int8_t *st = lds + l * ST;
-        switch (w) {
-            case 0: lane_predicates_part<N, 0>(st, 0, lim, f0, f1, cc, bad); break;
-            case 1: lane_predicates_part<N, 1>(st, 0, lim, f0, f1, cc, bad); break;
-            case 2: lane_predicates_part<N, 2>(st, 0, lim, f0, f1, cc, bad); break;
-            default: lane_predicates_part<N, 3>(st, 0, lim, f0, f1, cc, bad); break;
-        }
-        pf0[w][l] = f0;
-        if (w == 3) pf1[l] = f1;
-        if (w == 2) pcond[l] = cc;
-        pbad[w][l] = bad;
-    }
+    if (l < nb) phase_predicates<N>(w, l, lds + l * ST, 0, lim, pred);   // part w of every leaf
     lds_sync();
     LMPROBE(2)
-    if (l < nb) {                                        // mask words w and w+4
-        const bool bad = pbad[0][l] | pbad[1][l] | pbad[2][l] | pbad[3][l];
-        if (bad) {
-            const LanePred Pr = lane_predicates_exact<N>(lds + l * ST, 0, lim);
-            if (w == 0) { msk[l][0] = lane_mask_word<0>(Pr); msk[l][4] = lane_mask_word<4>(Pr); }
-            else if (w == 1) { msk[l][1] = lane_mask_word<1>(Pr); msk[l][5] = lane_mask_word<5>(Pr); }
-            else if (w == 2) { msk[l][2] = lane_mask_word<2>(Pr); msk[l][6] = lane_mask_word<6>(Pr); }
-            else { msk[l][3] = lane_mask_word<3>(Pr); }
-        } else {
-            const uint64_t F0 = pf0[0][l] | pf0[1][l] | pf0[2][l];
-            const uint32_t Cd = pcond[l], lv = (uint32_t)pf1[l];
-            if (w == 0) {
-                msk[l][0] = lane_mask_word_fast<0>(Cd, F0, lv, mfac);
-                msk[l][4] = lane_mask_word_fast<4>(Cd, F0, lv, mfac);
-            } else if (w == 1) {
-                msk[l][1] = lane_mask_word_fast<1>(Cd, F0, lv, mfac);
-                msk[l][5] = lane_mask_word_fast<5>(Cd, F0, lv, mfac);
-            } else if (w == 2) {
-                msk[l][2] = lane_mask_word_fast<2>(Cd, F0, lv, mfac);
-                msk[l][6] = lane_mask_word_fast<6>(Cd, F0, lv, mfac);
-            } else {
-                msk[l][3] = lane_mask_word_fast<3>(Cd, F0, lv, mfac);
-            }
-        }
-    }
+    if (l < nb) phase_mask_words<N>(w, l, lds + l * ST, 0, lim, pred, mfac, msk[l]);   // words w, w+4
     lds_sync();
     LMPROBE(3)
     {                                                    // pass bit, lane l < 16 of wave w
@@ -3305,7 +3238,7 @@ static Plan plan_pools(int n, int B, const spl_mcts_config *cfg) {
 }
 
 static bool valid_cfg(const spl_ctx *ctx, int B, const spl_mcts_config *cfg) {
-    if (!(ctx && ctx->n >= 2 && ctx->n <= 4 && B > 0 && cfg && cfg->num_sims > 0 && cfg->ratio_full > 0 &&
+    if (!(ok_ctx(ctx) && B > 0 && cfg && cfg->num_sims > 0 && cfg->ratio_full > 0 &&
           cfg->node_cap > 0 && cfg->edge_cap > 0 && cfg->pool_nodes >= 0 && cfg->pool_edges >= 0))
         return false;
     // global node ids are int32; page ids too
@@ -3561,7 +3494,7 @@ int spl_mcts_select_staged(spl_mcts *m, int8_t *leaf_state, uint64_t *leaf_mask,
 
 int spl_nn_stage_leaves(const spl_ctx *ctx, int B, const int8_t *leaf_state, const uint8_t *leaf_valid,
                         uint64_t *leaf_mask, void *stage, void *hs) {
-    if (!ctx || ctx->n < 2 || ctx->n > 4 || B < 0 || !stage_args_ok(leaf_state, leaf_mask, leaf_valid, stage))
+    if (!ok_ctx(ctx) || B < 0 || !stage_args_ok(leaf_state, leaf_mask, leaf_valid, stage))
         return SPL_EINVAL;
     if (!B) return 0;
     return launch_mask_staged(ctx->n, Pools{}, B, pack_lim(ctx->token_limit, ctx->rules), leaf_state, leaf_valid,

@@ -385,69 +385,6 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v) {
     return f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
 }
 
-// The search's NN leaves as k_leaf_mask lists them (ABI 11): segment j (trees 64 j .. 64 j + 63)
-// has count[j] leaves at idx[64 j ..]; the list is their concatenation in segment order.
-// Wave-collective: returns the list's length; with rowt / offv (ML ints each, the wave's own),
-// rowt[i] (i < ML) = the idx position of list entry b0 + i. A lane holds 8 consecutive
-// segments' counts (two 16-byte loads) and one DPP scan gives every segment's first entry; each
-// segment that reaches into the tile marks the slot where it starts (slot, and 64 j - start
-// in offv), and a prefix maximum over the slots gives every slot its segment.
-__device__ __forceinline__ int nn_list_rows(const int32_t *__restrict__ count, int nseg, int b0, int *rowt, int *offv) {
-    const int lane = threadIdx.x & 63;
-    if (rowt && lane < ML) rowt[lane] = -1;
-    int base = 0;
-    for (int c0 = 0; c0 < nseg; c0 += 512) {
-        const int j0 = c0 + 8 * lane;
-        int v[8];
-        if (j0 + 8 <= nseg) {
-            const int4 a = *reinterpret_cast<const int4 *>(count + j0), b = *reinterpret_cast<const int4 *>(count + j0 + 4);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; q++) v[q] = j0 + q < nseg ? count[j0 + q] : 0;
-        }
-        int own = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) own += v[q];
-        // inclusive scan of the lanes' sums on DPP: row_shr 1 / 2 / 4 / 8 inside each 16-lane
-        // row (lanes without a source add 0), then row_bcast 15 (rows 1, 3) and 31 (rows 2, 3)
-        int inc = own;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);
-        if (rowt) {
-            int ex = base + inc - own;                   // first list entry of segment j0
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                if (v[q] > 0 && ex + v[q] > b0 && ex < b0 + ML) {
-                    const int sl = max(ex - b0, 0);
-                    rowt[sl] = sl;
-                    offv[sl] = 64 * (j0 + q) - ex;
-                }
-                ex += v[q];
-            }
-        }
-        base += __builtin_amdgcn_readlane(inc, 63);
-    }
-    if (rowt) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int f = lane < ML ? rowt[lane] : -1;             // prefix maximum over slots 0 .. 31
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x111, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x112, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x114, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x118, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x142, 0xa, 0xf, false));
-        const int pos = f >= 0 ? b0 + lane + offv[f] : 0;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < ML) rowt[lane] = pos;
-    }
-    return base;
-}
-
 // PR (spl_nn_forward_mode): the leading bf16 parts of every matrix-product operand that enter
 // the MFMAs, 3 (SPL_NN_F32: the six products above), 2 (SPL_NN_BF16X2: hi hi, hi mid, mid hi) or
 // 1 (SPL_NN_BF16: hi hi); parts that are not multiplied are not loaded (weights) or not read
@@ -459,10 +396,10 @@ template <int NP, int PR, bool STG = false>
 // one workgroup per CU (LDS) = 2 waves per SIMD: the register budget is 256, and without
 // saying so the scheduler sinks the prefetched weight loads next to their MFMAs
 // idx / count (optional): the kernel evaluates the search's NN leaves as k_leaf_mask lists
-// them (nn_list_rows: B trees in segments of 64) — board / mask / output row idx[...] —
+// them (nn_stage.h leaf_list_scan: B trees in segments of 64) — board / mask / output row idx[...] —
 // instead of rows 0 .. B; tiles past the list's end exit at once.
 // sbuf (STG only): the staged leaf buffer; state / mask / idx / count are then not read, and
-// nn_list_rows and the byte scatter are not instantiated.
+// leaf_list_scan and the byte scatter are not instantiated.
 __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_nn_forward(int B, const int8_t *__restrict__ state,
                                                     const uint64_t *__restrict__ mask,
                                                     const float *__restrict__ W, float *__restrict__ pi_out,
@@ -509,7 +446,7 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         load_stage(IntC<0>());                           //  the tile's leaves)
         load_stage(IntC<1>());
     }
-    // the tile's idx positions (nn_list_rows): a copy per input wave, each mapped by its own
+    // the tile's idx positions (leaf_list_scan): a copy per input wave, each mapped by its own
     // wave (no barrier before the input loads; wave 7, which stages no input, needs only the
     // list's length); wave 0 also resolves the rows themselves into rowv for the epilogues
     int *rowt = reinterpret_cast<int *>(lds + BUFA + SAB + ML * 7 * 8);
@@ -518,8 +455,11 @@ __global__ __launch_bounds__(NNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if constexpr (STG) {
         cnt = min(__builtin_amdgcn_readfirstlane(scnt), B);
     } else if (count) {
+        int lpos;                                        // (16-byte count loads: two per lane)
         cnt = __builtin_amdgcn_readfirstlane(
-            nn_list_rows(count, (B + 63) >> 6, b0, w < 7 ? rowt_w : nullptr, offv_w));
+            nnstage::leaf_list_scan<ML, 8, true>(count, (B + 63) >> 6, b0, w < 7 ? rowt_w : nullptr, offv_w, lpos));
+        __builtin_amdgcn_wave_barrier();                 // (the scan's slot marks are rowt_w itself)
+        if (w < 7 && lane < ML) rowt_w[lane] = lpos;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the wave's own LDS writes,
         __builtin_amdgcn_wave_barrier();                        //  read back by its lanes)
     }

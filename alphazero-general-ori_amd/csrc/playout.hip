@@ -2,9 +2,11 @@
 // to the end of the game, only the outcomes leave the chip. The leaf evaluation of the
 // network-free search players (splendor/playout.py) and Monte-Carlo outcome estimates.
 //
-// A step is k_rollout's (splendor_env.hip) without the re-deal and without per-move outputs,
-// built from the same device functions (splendor_device.h), so a uniform playout repeats the
-// rollout's moves bit for bit. Mapping: a 256-thread workgroup owns 64 / P consecutive rows
+// A step is k_rollout's (splendor_env.hip) without the re-deal and without per-move outputs:
+// both kernels call the same phases (board_phases.h: table staging, predicates, mask words,
+// quad select, move by wave kind), so a uniform playout repeats the rollout's moves bit for
+// bit. What is this kernel's own: the live / active flags, the buy-first filter, the uniform
+// prior and the outcome sums. Mapping: a 256-thread workgroup owns 64 / P consecutive rows
 // and their (64 / P) P <= 64 tasks (task l = playout l % P of row r0 + l / P), a lane per
 // task, each task's board in its own LDS slot (8-byte rows, odd qword stride) for the whole
 // playout. A row's P tasks therefore always share a workgroup: the row's result is summed in
@@ -17,20 +19,17 @@
 // spl_playout_seq runs the same kernel with the stream base read from a device counter (SEQ:
 // step0 = (*call_seq mod 2^23) 256, so a captured launch draws new streams at every replay)
 // and, given the search's NN-leaf list (LIST), on the listed rows only: a workgroup then owns
-// 64 / P consecutive list entries, found by a scan of the segment counts, and one past the
+// 64 / P consecutive list entries, found by the network kernel's scan of the segment counts
+// (nn_stage.h leaf_list_scan), and one past the
 // end of the list leaves before it stages anything. Task keys stay tied to the row.
 #include <hip/hip_runtime.h>
 
 #include "../../include/splendor_amd.h"
-#include "splendor_device.h"
+#include "board_phases.h"
+#include "nn_stage.h"   // leaf_list_scan
+#include "spl_ctx.h"
 
 using namespace spl;
-
-struct spl_ctx {  // must match splendor_env.hip
-    int n;
-    int token_limit;
-    int rules;
-};
 
 namespace {
 
@@ -38,82 +37,6 @@ constexpr int WAVES = 4;
 constexpr int THREADS = 64 * WAVES;
 constexpr int PT = 64;                           // task slots per workgroup (lane per task)
 constexpr uint64_t BUY_BITS = 0x38000FFFull;     // actions 0-11 (buy visible), 27-29 (buy reserved)
-
-// COUNT elements of a constant table staged into LDS by the workgroup: every load is issued
-// (clamped index, no branch) before the first LDS store, as k_rollout stages its tables
-template <class T, int COUNT>
-struct TableRegs {
-    static constexpr int IT = (COUNT + THREADS - 1) / THREADS;
-    T v[IT];
-    __device__ __forceinline__ void fetch(const T *src, int tid) {
-#pragma unroll
-        for (int k = 0; k < IT; k++) v[k] = src[min(tid + k * THREADS, COUNT - 1)];
-    }
-    __device__ __forceinline__ void put(T *dst, int tid) const {
-#pragma unroll
-        for (int k = 0; k < IT; k++)
-            if (tid + k * THREADS < COUNT) dst[tid + k * THREADS] = v[k];
-    }
-};
-
-// The leaf list as spl_mcts_select_compact writes it: segment j (rows 64 j .. 64 j + 63) has
-// count[j] entries at leaf_index[64 j ..]; the list is their concatenation in segment order.
-// Wave-collective, registers only unless `slot` is given: returns the list's length, and with
-// slot / offv (PT ints each, the calling wave's own) lane i gets the leaf_index position of list
-// entry e0 + i in `pos` (meaningful for entries below the length). A lane holds 4 consecutive
-// segments' counts and one DPP scan gives every segment's first entry, 256 segments per pass;
-// each segment that reaches into [e0, e0 + PT) marks the slot where it starts (and 64 j - start
-// in offv), and a prefix maximum over the slots gives every slot its segment (the scan of
-// nn_list_rows, nnet.hip, on plain 4-byte loads: the counts need no alignment here).
-__device__ __forceinline__ int list_rows(const int32_t *__restrict__ count, int nseg, int e0, int *slot, int *offv,
-                                         int &pos) {
-    const int lane = lane_id();
-    if (slot) slot[lane] = -1;
-    int base = 0;
-    for (int c0 = 0; c0 < nseg; c0 += 4 * 64) {
-        const int j0 = c0 + 4 * lane;
-        int v[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = min(max(count[min(j0 + q, nseg - 1)], 0), j0 + q < nseg ? 64 : 0);
-        const int own = v[0] + v[1] + v[2] + v[3];
-        // inclusive scan of the lanes' sums on DPP: row_shr 1 / 2 / 4 / 8 inside each 16-lane
-        // row (lanes without a source add 0), then row_bcast 15 (rows 1, 3) and 31 (rows 2, 3)
-        int inc = own;
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xf, 0xf, true);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x142, 0xa, 0xf, false);
-        inc += __builtin_amdgcn_update_dpp(0, inc, 0x143, 0xc, 0xf, false);
-        if (slot) {
-            int ex = base + inc - own;                   // first list entry of segment j0
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                if (v[q] > 0 && ex + v[q] > e0 && ex < e0 + PT) {
-                    const int sl = max(ex - e0, 0);
-                    slot[sl] = sl;
-                    offv[sl] = 64 * (j0 + q) - ex;
-                }
-                ex += v[q];
-            }
-        }
-        base += __builtin_amdgcn_readlane(inc, 63);
-    }
-    pos = 0;
-    if (slot) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int f = slot[lane];                              // prefix maximum over slots 0 .. 63
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x111, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x112, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x114, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x118, 0xf, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x142, 0xa, 0xf, false));
-        f = max(f, __builtin_amdgcn_update_dpp(-1, f, 0x143, 0xc, 0xf, false));
-        if (f >= 0) pos = e0 + lane + offv[f];
-    }
-    return base;
-}
 
 // SEQ: the stream base is (*call_seq mod 2^23) SPL_PLAYOUT_SEQ_STREAMS instead of step0 (spl_playout_seq).
 // LIST (with SEQ): the rows are the entries of the leaf list; r0 / nr / nb then count list entries
@@ -143,22 +66,23 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
     __shared__ int32_t nstep[PT];      // moves played (max_steps until the game ends)
     __shared__ double ud[PT][4];       // draws 0..3 of each task's step stream
     __shared__ TabsLds tabs;
-    __shared__ uint64_t mfac[7 * 116];  // K_MASK_FACTORS (lane_mask_word_fast)
-    __shared__ uint32_t klist[4][PT];  // per move kind: task | action << 8 | player << 20
+    __shared__ uint64_t mfac[MASK_FACTOR_WORDS];
+    __shared__ uint32_t klist[4][PT];  // per move kind (file_move)
     __shared__ int kcount[4];
-    __shared__ uint64_t pf0[WAVES][PT], pf1[PT];
-    __shared__ uint32_t pcond[PT];
-    __shared__ uint8_t pbad[WAVES][PT];
+    __shared__ PredLds<PT> pred;
     __shared__ int erow[LIST ? PT : 1], eoff[LIST ? PT : 1];
     const int rpw = PT / P;                                  // rows (LIST: list entries) per workgroup
-    const int tid = threadIdx.x, w = tid >> 6, l = lane_id();
+    // the wave index in an SGPR: the per-wave choices of the shared phases (board_phases.h) are
+    // scalar branches. (k_rollout says why.)
+    const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), l = lane_id();
     const int r0 = blockIdx.x * rpw;
     int nr = min(rpw, B - r0), lpos = 0;
     if constexpr (LIST) {
         // every wave scans the counts in registers, so the exit is block-uniform with no barrier
-        // before it; wave 0 also resolves the workgroup's entries
-        const int total = list_rows(leaf_count, (B + 63) >> 6, r0, w == 0 ? erow : nullptr, w == 0 ? eoff : nullptr,
-                                    lpos);
+        // before it; wave 0 also resolves the workgroup's entries (plain 4-byte count loads: the
+        // counts need no alignment here)
+        const int total = nnstage::leaf_list_scan<PT, 4, false>(leaf_count, (B + 63) >> 6, r0, w == 0 ? erow : nullptr,
+                                                                w == 0 ? eoff : nullptr, lpos);
         if (r0 >= total) return;
         nr = min(rpw, total - r0);
     }
@@ -168,18 +92,8 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
     if constexpr (SEQ) step0 = (*call_seq & 0x7FFFFFu) * (uint32_t)SPL_PLAYOUT_SEQ_STREAMS;
     // prologue: the table loads go out first, the boards load while they are in flight
     {
-        TableRegs<double, 41 * 9> q_quot;
-        TableRegs<uint64_t, 240> q_cards;
-        TableRegs<uint64_t, 409> q_take, q_give;
-        TableRegs<int8_t, 409> q_rsv;
-        TableRegs<uint64_t, 7 * 116> q_fac;
-        q_quot.fetch(&K_QUOT[0][0], tid);
-        q_cards.fetch(&K_CARD_ROWS[0][0], tid);
-        q_take.fetch(K_ACT_TAKE, tid);
-        q_give.fetch(K_ACT_GIVE, tid);
-        q_rsv.fetch(K_ACT_RSV, tid);
-        q_fac.fetch(&K_MASK_FACTORS[0][0], tid);
-        const double recip = K_RECIP[min(tid, 8)];
+        TabsRegs<THREADS> q_tabs;
+        q_tabs.fetch(tid);
         if constexpr (LIST) {
             __builtin_amdgcn_wave_barrier();                 // (wave 0 has read its eoff[] above)
             if (w == 0) {
@@ -204,13 +118,7 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
             if (LIST ? r >= 0 : !active || active[r]) Cv::load(lds + t * ST, state + (size_t)r * Lx::S, u);
         }
         if (tid < 4) kcount[tid] = 0;
-        q_quot.put(&tabs.quot[0][0], tid);
-        q_cards.put(&tabs.cards[0][0], tid);
-        q_take.put(tabs.act_take, tid);
-        q_give.put(tabs.act_give, tid);
-        q_rsv.put(tabs.act_rsv, tid);
-        q_fac.put(mfac, tid);
-        if (tid < 9) tabs.recip[tid] = recip;
+        q_tabs.put(tabs, mfac, tid);
     }
     lds_sync();
     const int myrow = LIST ? erow[lrow] : r0 + lrow;         // (the key stays the row's, not the entry's)
@@ -226,51 +134,11 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
 #pragma unroll
             for (int k = 0; k < 2; k++) philox_pair(seed, board, step, k, ud[l][2 * k], ud[l][2 * k + 1]);
         }
-        if (on) {
-            uint64_t f0, f1;
-            uint32_t cc;
-            bool bad;
-            const int8_t *s = lds + l * ST;
-            switch (w) {
-                case 0: lane_predicates_part<N, 0>(s, pl[l], lim, f0, f1, cc, bad); break;
-                case 1: lane_predicates_part<N, 1>(s, pl[l], lim, f0, f1, cc, bad); break;
-                case 2: lane_predicates_part<N, 2>(s, pl[l], lim, f0, f1, cc, bad); break;
-                default: lane_predicates_part<N, 3>(s, pl[l], lim, f0, f1, cc, bad); break;
-            }
-            pf0[w][l] = f0;
-            if (w == 3) pf1[l] = f1;
-            if (w == 2) pcond[l] = cc;
-            pbad[w][l] = bad;
-        }
+        if (on) phase_predicates<N>(w, l, lds + l * ST, pl[l], lim, pred);
         __builtin_amdgcn_s_setprio(0);
         lds_sync();
-        // mask words w and w+4 of every live task (factorised words; boards outside the fast
-        // domain take the exact predicates and the per-action descriptor words)
-        if (on) {
-            const bool bad = pbad[0][l] | pbad[1][l] | pbad[2][l] | pbad[3][l];
-            if (bad) {
-                const LanePred Q = lane_predicates_exact<N>(lds + l * ST, pl[l], lim);
-                if (w == 0) { msk[l][0] = lane_mask_word<0>(Q); msk[l][4] = lane_mask_word<4>(Q); }
-                else if (w == 1) { msk[l][1] = lane_mask_word<1>(Q); msk[l][5] = lane_mask_word<5>(Q); }
-                else if (w == 2) { msk[l][2] = lane_mask_word<2>(Q); msk[l][6] = lane_mask_word<6>(Q); }
-                else { msk[l][3] = lane_mask_word<3>(Q); }
-            } else {
-                const uint64_t F0 = pf0[0][l] | pf0[1][l] | pf0[2][l];
-                const uint32_t C = pcond[l], lv = (uint32_t)pf1[l];
-                if (w == 0) {
-                    msk[l][0] = lane_mask_word_fast<0>(C, F0, lv, mfac);
-                    msk[l][4] = lane_mask_word_fast<4>(C, F0, lv, mfac);
-                } else if (w == 1) {
-                    msk[l][1] = lane_mask_word_fast<1>(C, F0, lv, mfac);
-                    msk[l][5] = lane_mask_word_fast<5>(C, F0, lv, mfac);
-                } else if (w == 2) {
-                    msk[l][2] = lane_mask_word_fast<2>(C, F0, lv, mfac);
-                    msk[l][6] = lane_mask_word_fast<6>(C, F0, lv, mfac);
-                } else {
-                    msk[l][3] = lane_mask_word_fast<3>(C, F0, lv, mfac);
-                }
-            }
-        }
+        // mask words w and w+4 of every live task
+        if (on) phase_mask_words<N>(w, l, lds + l * ST, pl[l], lim, pred, mfac, msk[l]);
         lds_sync();
         // the uniform prior over the input board's legal moves: once per active row, from the
         // first mask of its task 0 (pass alone when nothing else is legal). Block-uniform.
@@ -288,10 +156,9 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
                 }
             }
         }
-        // select: four lanes per task (task w*16 + l/4; lane q = l%4 holds mask words 2q, 2q+1):
-        // quad-wide counts by DPP, then the lane whose words hold the drawn index finds its bit.
-        // BUY_FIRST keeps only the buy bits of word 0 when there are any. Pass bit when nothing
-        // is legal; the task is filed by move kind.
+        // select: four lanes per task (task w*16 + l/4; lane q = l%4 holds mask words 2q, 2q+1),
+        // quad_select. BUY_FIRST keeps only the buy bits of word 0 when there are any. Pass when
+        // nothing is legal; the task is filed by move kind.
         {
             const int b = w * PER + (l >> 2), q = l & 3;
             const bool sel = b < nb && live[b];
@@ -305,26 +172,9 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
                 x0 = q == 0 ? x0 & BUY_BITS : 0;
                 x1 = 0;
             }
-            const int c0 = __popcll(x0), c = c0 + __popcll(x1);
-            const int k0 = quad_bcast<0>(c), k1 = quad_bcast<1>(c), k2 = quad_bcast<2>(c), k3 = quad_bcast<3>(c);
-            const int cnt = k0 + k1 + k2 + k3;
-            const int pre = (q > 0 ? k0 : 0) + (q > 1 ? k1 : 0) + (q > 2 ? k2 : 0);
-            int a = -1;
-            if (sel) {
-                if (cnt == 0) {
-                    if (q == 3) a = SPL_ACTIONS - 1;
-                } else {
-                    const int r = (int)(ud[b][0] * (double)cnt) - pre;
-                    if (r >= 0 && r < c) {
-                        const bool hi = r >= c0;
-                        a = 128 * q + (hi ? 64 : 0) + kth_bit64(hi ? x1 : x0, hi ? r - c0 : r);
-                    }
-                }
-            }
-            if (a >= 0) {
-                const int kind = move_kind_of(a);
-                klist[kind][atomicAdd(&kcount[kind], 1)] = (uint32_t)b | (uint32_t)a << 8 | (uint32_t)pl[b] << 20;
-            }
+            const QuadPick pk = quad_select(x0, x1, q, sel ? ud[b][0] : 0.0);
+            const int a = sel && pk.cnt == 0 && q == 3 ? SPL_ACTIONS - 1 : pk.a;
+            if (a >= 0) file_move(klist, kcount, b, a, pl[b]);
         }
         lds_sync();
         // move: wave k makes the moves of kind k, lane per task: chance draws 1-2, end check
@@ -335,15 +185,8 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
             if (l < kc) {
                 const int b = ke & 0xFF, a = (ke >> 8) & 0xFFF, p = ke >> 20;
                 int8_t *s = lds + b * ST;
-                const int r = (uint8_t)(bt(row(s, Lx::BANK), 6) + 1);   // the round after the move
-                Chance ch{&ud[b][0], 0, 0, 0, 1, 0.0, false, tabs.view()};
-                int nxt;
-                switch (w) {
-                    case MK_GEMS: nxt = make_move<N, MK_GEMS>(s, a, p, false, ch); break;
-                    case MK_BUY: nxt = make_move<N, MK_BUY>(s, a, p, false, ch); break;
-                    case MK_RESERVE: nxt = make_move<N, MK_RESERVE>(s, a, p, false, ch); break;
-                    default: nxt = make_move<N, MK_BUY_RESERVED>(s, a, p, false, ch); break;
-                }
+                int r;                                            // the round after the move
+                const int nxt = lane_move_of_kind<N>(w, s, a, p, &ud[b][0], tabs.view(), r);
                 float e[N];
                 check_end_round<N>(s, r, e);
                 bool ended = false;
@@ -379,8 +222,6 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
         if (unfinished && open && l == 0) atomicAdd(unfinished, (int32_t)__popcll(open));
     }
 }
-
-inline bool ok_ctx(const spl_ctx *c) { return c && c->n >= 2 && c->n <= 4; }
 
 // one launch of k_playout<N, SEQ, LIST>; a list launch is sized for B entries (the host cannot
 // know the list's length: the workgroups past its end leave at once)

@@ -69,17 +69,6 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t x) {
 // keeps the compiler from moving memory accesses across it.
 __device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// lane-per-board kernels that keep 64 boards in LDS (k_rollout, k_playout)
-// v of lane I of this lane's quad (DPP quad_perm broadcast; every lane must be active)
-template <int I>
-__device__ __forceinline__ int quad_bcast(int v) {
-    return __builtin_amdgcn_update_dpp(v, v, I | I << 2 | I << 4 | I << 6, 0xF, 0xF, false);
-}
-template <int N>
-struct RolloutLds {
-    static constexpr int STRIDE = (Lay<N>::ROWS % 2 ? Lay<N>::ROWS : Lay<N>::ROWS + 1) * 8;
-};
-
 // ------------------------------------------------------------------ row words
 __device__ __forceinline__ uint64_t &row(int8_t *s, int r) { return *reinterpret_cast<uint64_t *>(s + 8 * r); }
 __device__ __forceinline__ uint64_t row(const int8_t *s, int r) { return *reinterpret_cast<const uint64_t *>(s + 8 * r); }
@@ -131,7 +120,7 @@ __device__ __forceinline__ double philox_u01(uint64_t seed, uint32_t board, uint
 }
 
 // The transition tables (deck draws, per-action gem vectors). Default: constant memory;
-// a kernel may stage them in LDS (stage_tabs) and pass the LDS copy.
+// a kernel may stage them in LDS (board_phases.h TabsRegs) and pass the LDS copy.
 struct Tabs {
     const double (*quot)[9] = K_QUOT;
     const double *recip = K_RECIP;
@@ -147,17 +136,6 @@ struct TabsLds {          // LDS image of Tabs
     int8_t act_rsv[409];
     __device__ __forceinline__ Tabs view() const { return Tabs{quot, recip, cards, act_take, act_give, act_rsv}; }
 };
-// cooperative copy of the tables into LDS by `nthreads` threads (caller synchronises)
-__device__ __forceinline__ void stage_tabs(TabsLds &t, int tid, int nthreads) {
-    for (int i = tid; i < 41 * 9; i += nthreads) (&t.quot[0][0])[i] = (&K_QUOT[0][0])[i];
-    for (int i = tid; i < 240; i += nthreads) (&t.cards[0][0])[i] = (&K_CARD_ROWS[0][0])[i];
-    for (int i = tid; i < 409; i += nthreads) {
-        t.act_take[i] = K_ACT_TAKE[i];
-        t.act_give[i] = K_ACT_GIVE[i];
-        t.act_rsv[i] = K_ACT_RSV[i];
-    }
-    if (tid < 9) t.recip[tid] = K_RECIP[tid];
-}
 
 // Either an explicit stream of doubles (parity with recorded reference draws) or Philox.
 // Sequential draws reuse the second half of a Philox block. The transition tables travel

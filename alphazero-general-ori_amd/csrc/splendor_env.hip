@@ -33,16 +33,11 @@ __shared__ uint64_t spl_probe_last;
     }
 __device__ uint64_t *g_rollout_timing;
 #endif
-#include "splendor_device.h"
+#include "board_phases.h"
 #include "mcts_device.h"   // ST_PLAYER
+#include "spl_ctx.h"
 
 using namespace spl;
-
-struct spl_ctx {
-    int n;
-    int token_limit;
-    int rules;          // SPL_RULE_* flags
-};
 
 namespace {
 
@@ -291,24 +286,6 @@ __global__ __launch_bounds__(THREADS) void k_player_move(int B, const int8_t *__
 constexpr int RB = ROLLOUT_RB;   // boards per workgroup (<= 64: lane per board)
 #define RT_MARK(k) SPL_PROBE(k)
 
-// COUNT elements of a table held in registers across the workgroup's THREADS threads:
-// fetch() issues every load (clamped indices, no branch, so they all go out back to back),
-// put() stores them into LDS after the other fetches
-template <class T, int COUNT>
-struct StageRegs {
-    static constexpr int IT = (COUNT + THREADS - 1) / THREADS;
-    T v[IT];
-    __device__ __forceinline__ void fetch(const T *src, int tid) {
-#pragma unroll
-        for (int k = 0; k < IT; k++) v[k] = src[min(tid + k * THREADS, COUNT - 1)];
-    }
-    __device__ __forceinline__ void put(T *dst, int tid) const {
-#pragma unroll
-        for (int k = 0; k < IT; k++)
-            if (tid + k * THREADS < COUNT) dst[tid + k * THREADS] = v[k];
-    }
-};
-
 template <int N>
 __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__restrict__ state,
                                                      int8_t *__restrict__ player, int lim,
@@ -329,16 +306,17 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
     __shared__ double ud[RB][4];       // draws 0..3 of each board's step stream
     __shared__ double ub[WAVES][DEAL_DRAWS];
     __shared__ TabsLds tabs;
-    __shared__ uint64_t mfac[7 * 116];  // K_MASK_FACTORS (lane_mask_word_fast)
-    __shared__ uint32_t klist[4][RB];  // per move kind: board | action << 8 | player << 20
+    __shared__ uint64_t mfac[MASK_FACTOR_WORDS];
+    __shared__ uint32_t klist[4][RB];  // per move kind (file_move)
     __shared__ int kcount[4];
-    __shared__ uint64_t pf0[WAVES][RB], pf1[RB];
-    __shared__ uint32_t pcond[RB];
-    __shared__ uint8_t pbad[WAVES][RB];
+    __shared__ PredLds<RB> pred;
     __shared__ DealRec drec[2][RB];     // deals of games gd0+1, gd0+2 of every board
     __shared__ int32_t gd0[RB];
     const int b0 = blockIdx.x * RB, nb = min(RB, B - b0);
-    const int tid = threadIdx.x, w = tid >> 6, l = lane_id();
+    // the wave index in an SGPR: the per-wave choices of the shared phases (board_phases.h) are
+    // scalar branches. As a vector value their compares stay in the move loop: 3 % slower on
+    // the env benchmark, 1.3 % on playouts (profiles/shared_phases_ab.json).
+    const int tid = threadIdx.x, w = __builtin_amdgcn_readfirstlane(tid >> 6), l = lane_id();
     int8_t *const gst = state + (size_t)b0 * Lx::S;
 #if ROLLOUT_TIMING
     if (tid < 32) spl_probe_acc[tid] = 0;
@@ -357,32 +335,13 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
             const int b = ((tid + j * THREADS) >> 2) % RB;
             gt[j] = games_done[b0 + min(b, nb - 1)];      // (never null: spl_rollout_run checks)
         }
-        StageRegs<double, 41 * 9> q_quot;
-        StageRegs<uint64_t, 240> q_cards;
-        StageRegs<uint64_t, 409> q_take, q_give;
-        StageRegs<int8_t, 409> q_rsv;
-        StageRegs<uint64_t, 7 * 116> q_fac;
-        q_quot.fetch(&K_QUOT[0][0], tid);
-        q_cards.fetch(&K_CARD_ROWS[0][0], tid);
-        q_take.fetch(K_ACT_TAKE, tid);
-        q_give.fetch(K_ACT_GIVE, tid);
-        q_rsv.fetch(K_ACT_RSV, tid);
-        q_fac.fetch(&K_MASK_FACTORS[0][0], tid);
-        const double recip = K_RECIP[min(tid, 8)];
+        TabsRegs<THREADS> q_tabs;
+        q_tabs.fetch(tid);
         const int bi = min(tid, nb - 1);
         const int8_t p0 = player[b0 + bi];
         const int32_t g0 = games_done[b0 + bi];
-        constexpr int BI = Cv::QUAD ? (RB * Cv::UNITS + THREADS - 1) / THREADS : 1;
-        uint32_t d[BI][7];
-        if constexpr (Cv::QUAD) {
-#pragma unroll
-            for (int k = 0; k < BI; k++) {              // clamped index: every load is valid
-                const int i = min(tid + k * THREADS, nb * Cv::UNITS - 1), b = i / Cv::UNITS, u = i - b * Cv::UNITS;
-                const uint32_t *g = reinterpret_cast<const uint32_t *>(gst + (size_t)b * Lx::S) + 7 * u;
-#pragma unroll
-                for (int j = 0; j < 7; j++) d[k][j] = g[j];
-            }
-        }
+        BoardRegs<N, RB, THREADS> q_boards;
+        q_boards.fetch(gst, nb, tid);
         // the next deals of every board (one for launches of 4-47 moves, two beyond),
         // computed up front by four lanes per deal (3 tiers + nobles, lane_deal_part) so that
         // ending a game costs a row expansion, not the draws; a game ending beyond them draws
@@ -395,31 +354,14 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
             if (task < pre * RB * 4 && b < nb)
                 lane_deal_part<N>(seed, bbase + (uint32_t)(b0 + b), (uint32_t)(gt[j] + 1 + k), part, Tabs{}, drec[k][b]);
         }
-        if constexpr (Cv::QUAD) {
-#pragma unroll
-            for (int k = 0; k < BI; k++) {
-                const int i = tid + k * THREADS, b = i / Cv::UNITS, u = i - b * Cv::UNITS;
-                if (i < nb * Cv::UNITS) quad_rows_put(d[k], reinterpret_cast<uint64_t *>(lds + b * ST) + 4 * u);
-            }
-        } else {
-            for (int i = tid; i < nb * Cv::UNITS; i += THREADS) {
-                const int b = i / Cv::UNITS, u = i - b * Cv::UNITS;
-                Cv::load(lds + b * ST, gst + (size_t)b * Lx::S, u);
-            }
-        }
+        q_boards.put(lds, gst, nb, tid);
         if (tid < nb) {
             pl[tid] = p0;
             gdone[tid] = g0;
             gd0[tid] = g0;
         }
         if (tid < 4) kcount[tid] = 0;
-        q_quot.put(&tabs.quot[0][0], tid);
-        q_cards.put(&tabs.cards[0][0], tid);
-        q_take.put(tabs.act_take, tid);
-        q_give.put(tabs.act_give, tid);
-        q_rsv.put(tabs.act_rsv, tid);
-        q_fac.put(mfac, tid);
-        if (tid < 9) tabs.recip[tid] = recip;
+        q_tabs.put(tabs, mfac, tid);
     }
     const int pre = K >= 48 ? 2 : (K >= 4 ? 1 : 0);
     // every barrier of the move loop orders LDS only: the per-move outputs are write-only
@@ -441,22 +383,7 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
                 philox_pair(seed, bbase + (uint32_t)(b0 + l), step, k, ud[l][2 * k], ud[l][2 * k + 1]);
         }
         // predicates: wave w computes part w of every board's predicate set (lane per board)
-        if (ROLLOUT_ABLATE != 1 && l < nb) {
-            uint64_t f0, f1;
-            uint32_t cc;
-            bool bad;
-            const int8_t *s = lds + l * ST;
-            switch (w) {
-                case 0: lane_predicates_part<N, 0>(s, pl[l], lim, f0, f1, cc, bad); break;
-                case 1: lane_predicates_part<N, 1>(s, pl[l], lim, f0, f1, cc, bad); break;
-                case 2: lane_predicates_part<N, 2>(s, pl[l], lim, f0, f1, cc, bad); break;
-                default: lane_predicates_part<N, 3>(s, pl[l], lim, f0, f1, cc, bad); break;
-            }
-            pf0[w][l] = f0;
-            if (w == 3) pf1[l] = f1;
-            if (w == 2) pcond[l] = cc;
-            pbad[w][l] = bad;
-        }
+        if (ROLLOUT_ABLATE != 1 && l < nb) phase_predicates<N>(w, l, lds + l * ST, pl[l], lim, pred);
         if (ROLLOUT_PRIO) __builtin_amdgcn_s_setprio(0);
         RT_MARK(16)
         lds_sync();
@@ -465,43 +392,20 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
         // condition bits and colour levels; boards outside the fast domain take the exact
         // predicates and the per-action descriptor words
         if (ROLLOUT_ABLATE != 1 && l < nb) {
-            const bool bad = pbad[0][l] | pbad[1][l] | pbad[2][l] | pbad[3][l];
 #if ROLLOUT_TIMING
             {   // diagnostic: waves that take the exact predicate path (slot 18), lanes (19)
-                const uint64_t bm = __ballot(bad);
+                const uint64_t bm = __ballot(pred.any_bad(l));
                 if (l == 0 && bm) { atomicAdd((unsigned long long *)&spl_probe_acc[18], 1ull);
                                     atomicAdd((unsigned long long *)&spl_probe_acc[19], (unsigned long long)__popcll(bm)); }
             }
 #endif
-            if (bad) {
-                const LanePred P = lane_predicates_exact<N>(lds + l * ST, pl[l], lim);
-                if (w == 0) { msk[l][0] = lane_mask_word<0>(P); msk[l][4] = lane_mask_word<4>(P); }
-                else if (w == 1) { msk[l][1] = lane_mask_word<1>(P); msk[l][5] = lane_mask_word<5>(P); }
-                else if (w == 2) { msk[l][2] = lane_mask_word<2>(P); msk[l][6] = lane_mask_word<6>(P); }
-                else { msk[l][3] = lane_mask_word<3>(P); }
-            } else {
-                const uint64_t F0 = pf0[0][l] | pf0[1][l] | pf0[2][l];
-                const uint32_t C = pcond[l], lv = (uint32_t)pf1[l];
-                if (w == 0) {
-                    msk[l][0] = lane_mask_word_fast<0>(C, F0, lv, mfac);
-                    msk[l][4] = lane_mask_word_fast<4>(C, F0, lv, mfac);
-                } else if (w == 1) {
-                    msk[l][1] = lane_mask_word_fast<1>(C, F0, lv, mfac);
-                    msk[l][5] = lane_mask_word_fast<5>(C, F0, lv, mfac);
-                } else if (w == 2) {
-                    msk[l][2] = lane_mask_word_fast<2>(C, F0, lv, mfac);
-                    msk[l][6] = lane_mask_word_fast<6>(C, F0, lv, mfac);
-                } else {
-                    msk[l][3] = lane_mask_word_fast<3>(C, F0, lv, mfac);
-                }
-            }
+            phase_mask_words<N>(w, l, lds + l * ST, pl[l], lim, pred, mfac, msk[l]);
         }
         lds_sync();
         RT_MARK(1)
         // select: four lanes per board (board w*16 + l/4; lane q = l%4 holds mask words 2q,
-        // 2q+1): quad-wide counts by DPP, then the lane whose words hold the drawn index
-        // finds its bit, so no lane walks all seven words. Pass bit (:263) when nothing is
-        // legal; the board is filed by move kind.
+        // 2q+1), quad_select. Pass bit (:263) when nothing is legal; the board is filed by
+        // move kind.
         {
             const int b = w * PER + (l >> 2), q = l & 3;
             const bool on = ROLLOUT_ABLATE != 2 && b < nb;
@@ -510,25 +414,14 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
                 x0 = msk[b][2 * q];
                 if (q < 3) x1 = msk[b][2 * q + 1];
             }
-            const int c0 = __popcll(x0), c = c0 + __popcll(x1);
-            const int k0 = quad_bcast<0>(c), k1 = quad_bcast<1>(c), k2 = quad_bcast<2>(c), k3 = quad_bcast<3>(c);
-            const int cnt = k0 + k1 + k2 + k3;
-            const int pre = (q > 0 ? k0 : 0) + (q > 1 ? k1 : 0) + (q > 2 ? k2 : 0);
-            int a = -1;
+            const QuadPick pk = quad_select(x0, x1, q, on ? ud[b][0] : 0.0);
+            int a = pk.a;
             if (on) {
                 if (ROLLOUT_ABLATE == 1) {
-                    if (q == 0) a = 30 + (int)((step + b) % 5);
-                } else if (cnt == 0) {
-                    if (q == 3) {
-                        a = 408;
-                        x0 |= 1ull << (408 - 384);
-                    }
-                } else {
-                    const int r = (int)(ud[b][0] * (double)cnt) - pre;
-                    if (r >= 0 && r < c) {
-                        const bool hi = r >= c0;
-                        a = 128 * q + (hi ? 64 : 0) + kth_bit64(hi ? x1 : x0, hi ? r - c0 : r);
-                    }
+                    a = q == 0 ? 30 + (int)((step + b) % 5) : -1;
+                } else if (pk.cnt == 0 && q == 3) {
+                    a = 408;
+                    x0 |= 1ull << (408 - 384);
                 }
             }
             // the move's final mask goes to HBM from these registers (no LDS re-read)
@@ -537,10 +430,7 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
                 mo[0] = x0;
                 if (q < 3) mo[1] = x1;
             }
-            if (a >= 0) {
-                const int kind = move_kind_of(a);
-                klist[kind][atomicAdd(&kcount[kind], 1)] = (uint32_t)b | (uint32_t)a << 8 | (uint32_t)pl[b] << 20;
-            }
+            if (a >= 0) file_move(klist, kcount, b, a, pl[b]);
         }
         lds_sync();
         RT_MARK(5)
@@ -563,15 +453,8 @@ __global__ __launch_bounds__(THREADS) void k_rollout(int B, int K, int8_t *__res
                 b = ke & 0xFF;
                 const int a = (ke >> 8) & 0xFFF, p = ke >> 20;
                 int8_t *s = lds + b * ST;
-                const int r = (uint8_t)(bt(row(s, Lx::BANK), 6) + 1);   // the round after the move
-                Chance ch{&ud[b][0], 0, 0, 0, 1, 0.0, false, tabs.view()};
-                int nxt;
-                switch (w) {
-                    case MK_GEMS: nxt = make_move<N, MK_GEMS>(s, a, p, false, ch); break;
-                    case MK_BUY: nxt = make_move<N, MK_BUY>(s, a, p, false, ch); break;
-                    case MK_RESERVE: nxt = make_move<N, MK_RESERVE>(s, a, p, false, ch); break;
-                    default: nxt = make_move<N, MK_BUY_RESERVED>(s, a, p, false, ch); break;
-                }
+                int r;                                            // the round after the move
+                int nxt = lane_move_of_kind<N>(w, s, a, p, &ud[b][0], tabs.view(), r);
                 RT_MARK(6)
 #if ROLLOUT_TIMING
                 // per wave: move pipeline up to make_move's end (slots 28+w, lane 0's board)
@@ -847,7 +730,6 @@ __global__ __launch_bounds__(THREADS) void k_gather_examples(
 inline int check_launch() { return hipGetLastError() == hipSuccess ? 0 : SPL_EDEVICE; }
 inline dim3 wave_grid(int B) { return dim3((unsigned)((B + WAVES - 1) / WAVES)); }
 inline dim3 lane_grid(int B) { return dim3((unsigned)((B + 255) / 256)); }
-inline bool ok_ctx(const spl_ctx *c) { return c && c->n >= 2 && c->n <= 4; }
 // the `lim` argument of the mask-building kernels: token limit and rules (splendor_device.h)
 inline int ctx_lim(const spl_ctx *c) { return pack_lim(c->token_limit, c->rules); }
 
