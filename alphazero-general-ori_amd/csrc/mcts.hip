@@ -547,6 +547,31 @@ __device__ __forceinline__ GcScr gc_scr(int32_t *base, int nmax, int emax) {
     S.inv = q + 4 * m; S.queue = q + 5 * m; S.oec = q + 6 * m; S.own = q + 7 * m;
     return S;
 }
+// k_gc is alone on its CU (one workgroup of 8 waves; a second never fit), so a collection's working
+// arrays live in the CU's LDS as far as they fit: a small tree's phases are chains of
+// dependent gathers through these arrays (owner -> its bases -> the unit -> the link's remap),
+// at LDS latency instead of L2's. compact_tree takes the arrays from the arena in the order of
+// that dependence as their sizes become known (nodes, kept nodes, units); an array that does
+// not fit keeps its address in the global scratch, so the code below is the same for both.
+// Trees with more nodes than gc_lds_nodes() take no LDS at all (today's large trees, config 4).
+constexpr int GC_LDS_INTS = 40448;                       // 158 KB of the CU's 160
+struct GcArena {
+    int32_t *p;
+    int left;                                            // ints (even: 8-byte steps)
+    __device__ __forceinline__ int32_t *take(int ints, int32_t *fallback) {
+        ints = (ints + 1) & ~1;
+        if (ints > left) return fallback;
+        int32_t *r = p;
+        p += ints; left -= ints;
+        return r;
+    }
+};
+// the node count up to which a collection works in LDS (remap and nvs always fit below it);
+// limit < 0: the arena's own budget (spl_diag_gc_lds_limit)
+__host__ __device__ inline int gc_lds_nodes(int limit) {
+    const int cap = GC_LDS_INTS / 2 - 2;
+    return limit < 0 || limit > cap ? cap : limit;
+}
 
 // mark[i] = 1 for the root (local rootl) and every node reachable from it through child
 // links, 0 else (breadth-first in batches of up to 64 queued nodes, their visit records —
@@ -599,6 +624,25 @@ __device__ void mark_linked(const Pools &P, int t, int rootl, int32_t *mark, int
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // (HIP's uint4 struct defeats SROA)
+// a node record as its four 16-byte quarters, for compact_tree's move of whole records (the
+// few fields it needs by their offsets: four loads and four stores per record, and nothing for
+// the compiler to stage through the stack as it does for a Node copied around field updates)
+struct NodeRaw {
+    u32x4 q[4];
+    __device__ __forceinline__ int bchild() const { return (int)q[0].x; }
+    __device__ __forceinline__ bool term() const { return (q[1].y & 0xFFu) != 0; }
+    __device__ __forceinline__ uint64_t ebq() const { return (uint64_t)q[2].x | ((uint64_t)q[2].y << 32); }
+    __device__ __forceinline__ uint64_t vbq() const { return (uint64_t)q[2].z | ((uint64_t)q[2].w << 32); }
+    __device__ __forceinline__ int ec() const { return (int)(int16_t)(q[3].x & 0xFFFFu); }
+    __device__ __forceinline__ void set_runs(uint64_t e, uint64_t v) {
+        q[2] = u32x4{(uint32_t)e, (uint32_t)(e >> 32), (uint32_t)v, (uint32_t)(v >> 32)};
+    }
+    __device__ __forceinline__ void clear_hints() { q[0].y = 0xFFFFFFFFu; q[0].z = 0xFFFFFFFFu; }   // h2, h3 = -1
+};
+static_assert(sizeof(NodeRaw) == sizeof(Node) && offsetof(Node, h.bchild) == 0 && offsetof(Node, h.h2) == 4 &&
+                  offsetof(Node, h.h3) == 8 && offsetof(Node, h.term) == 20 && offsetof(Node, c.ebq) == 32 &&
+                  offsetof(Node, c.vbq) == 40 && offsetof(Node, c.ec) == 48,
+              "NodeRaw's field offsets");
 
 // k_gc collects one tree per workgroup of GCT threads (block-wide scans through LDS), so a
 // large tree's collection (config 4: ~40 K nodes, ~0.5 M edge units) is spread over 8 waves
@@ -655,12 +699,18 @@ constexpr int GC_NOFIT = -2;   // compact_tree: the compacted tree would not fit
 #define GC_CR 4            // node-board units per thread per round trip of the board move (x2)
 #endif
 template <int CR = 4>   // board units per thread per round trip of the node-board move (x2)
-__device__ int compact_tree(const Pools &P, int t, int root, int root_round, const GcScr &S, GcLds &L,
-                            int bunits, bool linked = false) {
+__device__ int compact_tree(const Pools &P, int t, int root, int root_round, const GcScr &G, int32_t *lds,
+                            int lds_nodes, GcLds &L, int bunits, bool linked = false) {
     const int tid = threadIdx.x;
     TreeHdr *H = P.hdr + t;
     const int nc = H->node_count;
     const int rootl = root >= 0 ? node_l(P, root) : -1;
+    // the working arrays: LDS as far as the arena reaches (all sizes are workgroup-uniform)
+    GcScr S = G;
+    GcArena A{lds, nc <= lds_nodes ? GC_LDS_INTS : 0};
+    S.remap = A.take(nc, G.remap);
+    S.nvs = A.take(nc, G.nvs);
+    if (linked) S.queue = A.take(nc, G.queue);           // (the breadth-first queue: up to nc entries)
     int32_t *remap = S.remap;
 #if GC_PROBE
     uint64_t gacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, glast = __builtin_readcyclecounter();
@@ -681,6 +731,12 @@ __device__ int compact_tree(const Pools &P, int t, int root, int root_round, con
         kept += tot;
     }
     __syncthreads();
+    // the new-local arrays the unit staging gathers through own[k] first, then the rest
+    S.cs = A.take(kept, G.cs); S.oec = A.take(kept, G.oec);
+    S.ost = reinterpret_cast<int64_t *>(A.take(2 * kept, reinterpret_cast<int32_t *>(G.ost)));
+    S.ovb = reinterpret_cast<int64_t *>(A.take(2 * kept, reinterpret_cast<int32_t *>(G.ovb)));
+    S.cnt = A.take(kept, G.cnt); S.inv = A.take(kept, G.inv);
+    if (!linked) S.queue = A.take(kept, G.queue);
     GPROBE(0)
     // new unit position of every kept node's allocation (run + visit records): packed in local
     // order, an allocation that would straddle an edge page starts the next page. The sizes
@@ -750,36 +806,44 @@ __device__ int compact_tree(const Pools &P, int t, int root, int root_round, con
     // caller falls back to pruning / emptying.
     if (run > H->epg * UPG) return GC_NOFIT;
     __syncthreads();
+    // the two sequential, coalesced arrays last, if room remains
+    S.own = A.take(run, G.own);
+    S.buf = reinterpret_cast<uint64_t *>(A.take(2 * run, reinterpret_cast<int32_t *>(G.buf)));
     // node records, chunk by chunk in local order (new slot <= old slot): reads, then writes
     int my_units = 0;
     for (int base = 0; base < nc; base += GCT) {
         const int i = base + tid;
         const int ni = i < nc ? remap[i] : -1;
         uint64_t k0 = 0, k1 = 0;
-        Node nd{};
+        NodeRaw nd{};
         int vs = 0;
         if (ni >= 0) {
             const int g = node_g(P, t, i);
-            k0 = P.nkey0[g]; k1 = P.nkey1[g];
-            nd = P.nd[g];
             vs = S.nvs[i];
+            k0 = P.nkey0[g]; k1 = P.nkey1[g];
+            nd = *reinterpret_cast<const NodeRaw *>(P.nd + g);
         }
         __syncthreads();
         if (ni >= 0) {
             const int ng = node_g(P, t, ni);
-            const bool term = nd.h.term;
-            const int ec = nd.c.ec, vcnt = term ? 0 : nd.c.vcnt();
+            const bool term = nd.term();
+            const uint64_t ebq = nd.ebq(), vbq = nd.vbq();
+            const int ec = nd.ec(), vcnt = term ? 0 : (int)(vbq >> 48);
             const int sz = term ? 0 : ec + REC_UNITS * vcnt;
-            Node w = nd;                                 // (a terminal node's values as they are)
-            S.queue[ni] = term ? -1 : nd.h.bchild;       // (the arg-max's link, remapped below)
-            S.ost[ni] = nd.c.eb(); S.ovb[ni] = nd.c.vb(); S.oec[ni] = term ? 0 : ec;
+            NodeRaw w = nd;                              // (a terminal node's values as they are)
+            const int bch = term ? -1 : nd.bchild();     // (the arg-max's link, remapped below)
+            const int64_t oeb = (int64_t)(ebq & LOW48), ovb = (int64_t)(vbq & LOW48);
             if (!term) {
-                w.c.set_eb(ec > 0 ? unit_g(P, t, vs) : 0, vcnt);
-                w.c.set_vb(vcnt > 0 ? unit_g(P, t, vs + ec) : 0, vcnt);
+                NodeCold c;
+                c.set_eb(ec > 0 ? unit_g(P, t, vs) : 0, vcnt);
+                c.set_vb(vcnt > 0 ? unit_g(P, t, vs + ec) : 0, vcnt);
+                w.set_runs(c.ebq, c.vbq);
             }
-            w.h.h2 = -1; w.h.h3 = -1;
+            w.clear_hints();
             P.nkey0[ng] = k0; P.nkey1[ng] = k1;
-            P.nd[ng] = w;
+            *reinterpret_cast<NodeRaw *>(P.nd + ng) = w;
+            S.queue[ni] = bch;
+            S.ost[ni] = oeb; S.ovb[ni] = ovb; S.oec[ni] = term ? 0 : ec;
             S.cs[ni] = vs; S.cnt[ni] = sz; S.inv[ni] = i;
             my_units += sz;
         }
@@ -1059,60 +1123,84 @@ __device__ void begin_search(const Pools &P, const SearchCfg &C, int t, const in
 
 // Garbage collection queued by k_backup (a leaf did not fit mid-search: gc_state 1) and by
 // search starts (3 must, 5 should), one workgroup of GCT threads per queued tree, GC_WG
-// workgroups sharing the queue (a workgroup's scratch: gc_stride ints of P.gscr). Exactly
-// begin_search's policy: compact (rounds > the root's), prune to the linked nodes, empty.
+// workgroups popping the queue from a cursor (a workgroup's scratch: the CU's LDS, and
+// gc_stride ints of P.gscr for what does not fit there). Exactly begin_search's policy:
+// compact (rounds > the root's), prune to the linked nodes, empty.
 // Queued trees come in bursts (games start together and commit together, so trees fill up
 // together): "should" collections beyond GC_SHOULD_CAP per launch stay queued for the next
-// launches (k_gc runs behind every self-play backup and commit). That is exact: a deferred
-// tree searches on as it is (its search fits), and if a leaf finds no room meanwhile the
-// simulation is withdrawn (gc_state 5 -> 1) and the tree collected in the next launch. A
-// collection is a chain of dependent phases in one workgroup, so a launch costs about its
-// slowest collection however many run beside it: the cap is one round of workgroups (a
-// smaller cap spreads a burst over more launches that each pay that latency — round 4
-// measured 16 per launch at 195 us per launch, ~390 us per iteration at config 3).
+// launches (k_gc runs behind every self-play commit). That is exact: a deferred tree searches
+// on as it is (its search fits), and if a leaf finds no room meanwhile the simulation is
+// withdrawn (gc_state 5 -> 1) and the tree collected in the next launch. A collection is a
+// chain of dependent phases in one workgroup, so a launch costs at least its slowest
+// collection; with the cursor the workgroups that finish small trees take the next entries
+// meanwhile, so the cap bounds a launch's total work, not its rounds. Config 3 queues ~276
+// trees per commit cycle: a cap of 256 (one round of the former static stride) left ~20 of
+// them to a second launch that again cost its slowest collection; 1,024 and no cap at all
+// measured the same (0.4229 / 0.4230 ms per iteration against 0.4280 at 256,
+// profiles/gc_lds.json), and the cap stays so that a launch's length has a bound.
 #ifndef GC_WG
-#define GC_WG 256               // one per CU (168 VGPRs x 8 waves: a second one does not fit;
-#endif                          //  512 measured no change, r05)
+#define GC_WG 256               // one per CU (154 VGPRs x 8 waves and the LDS arena: a second one
+#endif                          //  does not fit; 512 measured no change, r05)
 #ifndef GC_SHOULD_CAP
-#define GC_SHOULD_CAP GC_WG
+#define GC_SHOULD_CAP 1024
 #endif
+// which way the collections went (spl_diag_gc_paths): [0] collections with LDS scratch [1] with
+// the global scratch alone [2] most queue entries one workgroup took in a launch [3] launches
+// that had collections queued
+__device__ unsigned long long g_gc_paths[4];
 template <int N>
-__global__ __launch_bounds__(GCT) void k_gc(Pools P, SearchCfg C) {
+__global__ __launch_bounds__(GCT) void k_gc(Pools P, SearchCfg C, int lds_limit) {
+    __shared__ __align__(16) int32_t arena[GC_LDS_INTS];
     __shared__ GcLds L;
-    __shared__ int keep_s;
+    __shared__ int keep_s, pop_s;
     const int tid = threadIdx.x;
     const int tail = P.counters[2];                      // no pushes while k_gc runs
     const int ftail = P.counters[5];
     if (tail == 0 && ftail == 0) return;                 // (the usual case)
     const GcScr S = gc_scr(P.gscr + (size_t)blockIdx.x * P.gc_stride, P.nmax, P.emax);
-    for (int k = blockIdx.x; k < tail; k += gridDim.x) {     // garbage collection
+    const int lds_nodes = gc_lds_nodes(lds_limit);
+    // garbage collection: the workgroups pop the queue's entries from a cursor (counters[6]),
+    // so one that finishes a small tree takes the next entry while a large one is still at work
+    int taken = 0;
+    for (;;) {
+        if (tid == 0) {
+            const int k = atomicAdd(&P.counters[6], 1);
+            int keep = 0;
+            if (k < tail) {
+                const int t = P.gcq[k];
+                if (P.hdr[t].gc_state == 5 && atomicAdd(&P.counters[8], 1) >= GC_SHOULD_CAP) {
+                    keep = 1;                            // deferred: stays queued
+                    P.gcq2[atomicAdd(&P.counters[9], 1)] = t;
+                }
+            }
+            pop_s = k; keep_s = keep;
+        }
+        __syncthreads();
+        const int k = pop_s;
+        const bool deferred = keep_s != 0;
+        __syncthreads();                                 // (both read before the next pop)
+        if (k >= tail) break;
+        taken++;
+        if (deferred) continue;
         const int t = P.gcq[k];
         TreeHdr *H = P.hdr + t;
         const int st = H->gc_state;
-        if (tid == 0) {
-            int keep = 0;
-            if (st == 5 && atomicAdd(&P.counters[8], 1) >= GC_SHOULD_CAP) {
-                keep = 1;                                // deferred: stays queued
-                P.gcq2[atomicAdd(&P.counters[9], 1)] = t;
-            }
-            keep_s = keep;
-        }
-        __syncthreads();
-        if (keep_s) continue;
         int root = H->root;
         const int nst = st == 1 ? 2 : 0;
         if (st == 1 || st == 3 || st == 5) {
+            if (tid == 0) atomicAdd(&g_gc_paths[H->node_count <= lds_nodes ? 0 : 1], 1ull);
             // mid-search (1: the descent then repeats): rounds above the root's; search start:
             // above the root round
             const int rr = st == 1 && root >= 0 ? P.nd[root].h.round : H->root_round;
             const int r0 = root;
-            root = compact_tree<GC_CR>(P, t, r0, rr, S, L, NodeBoard<N>::UNITS);
+            root = compact_tree<GC_CR>(P, t, r0, rr, S, arena, lds_nodes, L, NodeBoard<N>::UNITS);
             // capacity pressure (search start: the search would not fit; any: the compacted
             // layout would not fit the page table): prune to the linked nodes, else empty
             bool prune = root == GC_NOFIT;
             if (!prune && st != 1) prune = !tree_fits(P, C, H) && root >= 0;
             if (prune) {
-                root = compact_tree<GC_CR>(P, t, root == GC_NOFIT ? r0 : root, rr, S, L, NodeBoard<N>::UNITS, true);
+                root = compact_tree<GC_CR>(P, t, root == GC_NOFIT ? r0 : root, rr, S, arena, lds_nodes, L,
+                                           NodeBoard<N>::UNITS, true);
                 if (tid == 0) H->prunes += 1;
             }
             __syncthreads();
@@ -1133,7 +1221,8 @@ __global__ __launch_bounds__(GCT) void k_gc(Pools P, SearchCfg C) {
         }
         __syncthreads();
     }
-// finished games' example rows (k_commit): the staging rows stay untouched until the
+    if (tid == 0 && taken > 0) atomicMax(&g_gc_paths[2], (unsigned long long)taken);
+    // finished games' example rows (k_commit): the staging rows stay untouched until the
     // tree's next commit, a later iteration
     for (int k = blockIdx.x; k < ftail; k += gridDim.x) {
         const int2 e = P.flq[k];
@@ -1157,9 +1246,11 @@ __global__ __launch_bounds__(GCT) void k_gc(Pools P, SearchCfg C) {
             P.gcq[i] = __hip_atomic_load(&P.gcq2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         if (tid == 0) {
+            if (tail > 0) g_gc_paths[3] += 1;
             P.counters[2] = nk;
             P.counters[5] = 0;
             P.counters[4] = 0;
+            P.counters[6] = 0;
             P.counters[8] = 0;
             P.counters[9] = 0;
         }
@@ -3430,11 +3521,31 @@ int spl_mcts_set_roots(spl_mcts *m, const int8_t *roots, int keep_tree, int forc
     return spl_mcts_set_roots_active(m, roots, nullptr, keep_tree, force_full, hs);
 }
 
+static int g_gc_lds_limit = -1;   // nodes; < 0: the arena's own budget (spl_diag_gc_lds_limit)
 // garbage collection queued by search starts / backups (usually none; in bursts up to
-// thousands of trees, GC_WG single-wave workgroups share the queue)
+// thousands of trees, GC_WG workgroups share the queue)
 static void launch_gc(spl_mcts *m, hipStream_t hs) {
     const unsigned gcw = (unsigned)(m->B < GC_WG ? m->B : GC_WG);
-    SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_gc<N>, dim3(gcw), dim3(GCT), 0, hs, m->P, m->cfg));
+    SPL_DISPATCH(m->n, hipLaunchKernelGGL(k_gc<N>, dim3(gcw), dim3(GCT), 0, hs, m->P, m->cfg, g_gc_lds_limit));
+}
+
+// diagnostics of k_gc's two scratch tiers and its queue (always compiled, not part of the ABI):
+// out4 = g_gc_paths, see there
+extern "C" int spl_diag_gc_paths(unsigned long long *out4, int reset) {
+    if (!out4 || hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_gc_paths), 4 * 8) != hipSuccess) return SPL_EDEVICE;
+    if (reset) {
+        unsigned long long z[4] = {0, 0, 0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_gc_paths), z, sizeof(z)) != hipSuccess) return SPL_EDEVICE;
+    }
+    return 0;
+}
+// trees with more than `nodes` nodes collect in the global scratch alone (negative: the LDS
+// arena's own budget); an argument of the launches made from now on (a captured graph keeps
+// the value it was captured with). Returns the previous value.
+extern "C" int spl_diag_gc_lds_limit(int nodes) {
+    const int prev = g_gc_lds_limit;
+    g_gc_lds_limit = nodes < 0 ? -1 : nodes;
+    return prev;
 }
 
 int spl_mcts_set_roots_active(spl_mcts *m, const int8_t *roots, const uint8_t *active, int keep_tree,

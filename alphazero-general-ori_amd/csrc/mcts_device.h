@@ -233,7 +233,8 @@ struct Pools {
     int32_t *out_scdiff, *out_meta;      // out_cap x 4, out_cap x 4 (board id, game, index, player)
     int32_t *counters;                   // [0] queued examples [1] dropped [2] GC queue
                                          // [5] example-row queue [4] k_gc workgroups done
-                                         // [6] [7] unused
+                                         // [6] k_gc's queue cursor (the next entry to pop;
+                                         // zero between launches) [7] unused
                                          // [8] should-collections taken by this k_gc launch
                                          // [9] deferred entries (gcq2)
     int32_t *gcq;                        // B: trees whose garbage collection k_gc runs
