@@ -22,6 +22,11 @@
 // 64 / P consecutive list entries, found by the network kernel's scan of the segment counts
 // (nn_stage.h leaf_list_scan), and one past the
 // end of the list leaves before it stages anything. Task keys stay tied to the row.
+//
+// spl_playout_mix (MIX, with SEQ) blends instead of storing: v = (1 - lambda) v + lambda mean in
+// the caller's value buffer (the network's), lambda one device f32 clamped to 0..1; the priors
+// stay the caller's, so no pi_out and no steps_out. A clamped lambda of 0 ends every workgroup
+// before it stages anything.
 #include <hip/hip_runtime.h>
 
 #include "../../include/splendor_amd.h"
@@ -41,7 +46,9 @@ constexpr uint64_t BUY_BITS = 0x38000FFFull;     // actions 0-11 (buy visible), 
 // SEQ: the stream base is (*call_seq mod 2^23) SPL_PLAYOUT_SEQ_STREAMS instead of step0 (spl_playout_seq).
 // LIST (with SEQ): the rows are the entries of the leaf list; r0 / nr / nb then count list entries
 // and erow[] holds each entry's row (-1: an index outside 0 .. B - 1, which runs nothing).
-template <int N, bool SEQ, bool LIST>
+// MIX (with SEQ): result is read and written, result = (1 - *lambda) result + *lambda mean, by the
+// thread that stores the mean otherwise; pi_out and steps_out are not written.
+template <int N, bool SEQ, bool LIST, bool MIX = false>
 __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t *__restrict__ state,
                                                      const int8_t *__restrict__ player,
                                                      const uint8_t *__restrict__ active, int lim, int policy,
@@ -50,8 +57,17 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
                                                      int32_t *__restrict__ steps_out, int32_t *unfinished,
                                                      const int32_t *__restrict__ leaf_index,
                                                      const int32_t *__restrict__ leaf_count,
-                                                     const uint32_t *__restrict__ call_seq) {
+                                                     const uint32_t *__restrict__ call_seq,
+                                                     const float *__restrict__ lambda) {
     static_assert(SEQ || !LIST, "the list entry reads its stream base on the device");
+    static_assert(SEQ || !MIX, "the mixed entry reads its stream base on the device");
+    // one scalar for the whole grid: a block-uniform exit with no barrier before it (a NaN
+    // clamps to 0: fmaxf returns its other operand)
+    float lam = 0.f;
+    if constexpr (MIX) {
+        lam = fminf(fmaxf(*lambda, 0.f), 1.f);
+        if (lam == 0.f) return;
+    }
     using Lx = Lay<N>;
     using Cv = Conv<N>;
     constexpr int ST = RolloutLds<N>::STRIDE;
@@ -142,7 +158,7 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
         lds_sync();
         // the uniform prior over the input board's legal moves: once per active row, from the
         // first mask of its task 0 (pass alone when nothing else is legal). Block-uniform.
-        if (t == 0 && pi_out) {
+        if (!MIX && t == 0 && pi_out) {
             for (int b = 0; b < nb; b += P) {
                 if (!act[b]) continue;
                 int cnt = 0;
@@ -212,31 +228,37 @@ __global__ __launch_bounds__(THREADS) void k_playout(int B, int P, const int8_t 
         if (act[rr * P]) {
             float sum = 0.f;
             for (int j = 0; j < P; j++) sum += outc[rr * P + j][i];
-            result[(size_t)(LIST ? erow[rr] : r0 + rr) * N + i] = sum / (float)P;
+            if constexpr (MIX) {
+                float *out = result + (size_t)(LIST ? erow[rr] : r0 + rr) * N + i;
+                *out = (1.0f - lam) * *out + lam * (sum / (float)P);
+            } else {
+                result[(size_t)(LIST ? erow[rr] : r0 + rr) * N + i] = sum / (float)P;
+            }
         }
     }
     if (w == 0) {
         const bool on = l < nb && act[l];
-        if (steps_out && on) steps_out[LIST ? (size_t)myrow * P + (l - lrow * P) : (size_t)r0 * P + l] = nstep[l];
+        if (!MIX && steps_out && on)
+            steps_out[LIST ? (size_t)myrow * P + (l - lrow * P) : (size_t)r0 * P + l] = nstep[l];
         const uint64_t open = __ballot(l < nb && live[l]);   // still playing after max_steps moves
         if (unfinished && open && l == 0) atomicAdd(unfinished, (int32_t)__popcll(open));
     }
 }
 
-// one launch of k_playout<N, SEQ, LIST>; a list launch is sized for B entries (the host cannot
+// one launch of k_playout<N, SEQ, LIST, MIX>; a list launch is sized for B entries (the host cannot
 // know the list's length: the workgroups past its end leave at once)
-template <bool SEQ, bool LIST>
+template <bool SEQ, bool LIST, bool MIX = false>
 int launch_playout(const spl_ctx *c, int B, const int8_t *state, const int8_t *player, const uint8_t *active,
                    int policy, int playouts, int max_steps, uint64_t seed, uint32_t step0, uint32_t board_base,
                    float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished, const int32_t *leaf_index,
-                   const int32_t *leaf_count, const uint32_t *call_seq, void *hs) {
+                   const int32_t *leaf_count, const uint32_t *call_seq, void *hs, const float *lambda = nullptr) {
     const int rpw = PT / playouts;
     const dim3 grid((unsigned)(((long long)B + rpw - 1) / rpw));
 #define SPL_PLAYOUT_LAUNCH(NP)                                                                            \
-    hipLaunchKernelGGL((k_playout<NP, SEQ, LIST>), grid, dim3(THREADS), 0, (hipStream_t)hs, B, playouts,  \
-                       state, player, active, pack_lim(c->token_limit, c->rules), policy, max_steps,      \
-                       seed, step0, board_base, result, pi_out, steps_out, unfinished, leaf_index,        \
-                       leaf_count, call_seq)
+    hipLaunchKernelGGL((k_playout<NP, SEQ, LIST, MIX>), grid, dim3(THREADS), 0, (hipStream_t)hs, B,      \
+                       playouts, state, player, active, pack_lim(c->token_limit, c->rules), policy,       \
+                       max_steps, seed, step0, board_base, result, pi_out, steps_out, unfinished,         \
+                       leaf_index, leaf_count, call_seq, lambda)
     switch (c->n) {
         case 2: SPL_PLAYOUT_LAUNCH(2); break;
         case 3: SPL_PLAYOUT_LAUNCH(3); break;
@@ -278,4 +300,22 @@ extern "C" int spl_playout_seq(const spl_ctx *c, int B, const int8_t *state, con
     return launch_playout<true, false>(c, B, state, nullptr, active, policy, playouts, max_steps, seed, 0,
                                        board_base, result, pi_out, steps_out, unfinished, nullptr, nullptr, call_seq,
                                        hs);
+}
+
+extern "C" int spl_playout_mix(const spl_ctx *c, int B, const int8_t *state, const uint8_t *active,
+                               const int32_t *leaf_index, const int32_t *leaf_count, int policy, int playouts,
+                               int max_steps, uint64_t seed, const uint32_t *call_seq, uint32_t board_base,
+                               const float *lambda, float *v, int32_t *unfinished, void *hs) {
+    if (!ok_ctx(c) || !state || !v || !call_seq || !lambda || B < 0 || policy < SPL_PLAYOUT_UNIFORM ||
+        policy > SPL_PLAYOUT_BUY_FIRST || playouts < 1 || playouts > 64 || max_steps < 1 ||
+        max_steps > SPL_PLAYOUT_SEQ_STREAMS || !leaf_index != !leaf_count || (active && leaf_index))
+        return SPL_EINVAL;
+    if (!B) return 0;
+    if (leaf_index)
+        return launch_playout<true, true, true>(c, B, state, nullptr, nullptr, policy, playouts, max_steps, seed, 0,
+                                                board_base, v, nullptr, nullptr, unfinished, leaf_index, leaf_count,
+                                                call_seq, hs, lambda);
+    return launch_playout<true, false, true>(c, B, state, nullptr, active, policy, playouts, max_steps, seed, 0,
+                                             board_base, v, nullptr, nullptr, unfinished, nullptr, nullptr, call_seq,
+                                             hs, lambda);
 }

@@ -6,6 +6,7 @@ Modules:
   SplendorGame  the reference's Game interface (SplendorGame.py:11-86), engine-backed
   SplendorPlayers  RandomPlayer / GreedyPlayer for the sequential Arena (one-board kernel calls)
   playout       PlayoutEvaluator: leaf values from random playouts (network-free search players
-                and the rollout bootstrap of Coach.learn), safe under graph capture
+                and the rollout bootstrap of Coach.learn), safe under graph capture;
+                MixedEvaluator: the network's priors, values mixed with the playouts'
   arena, pit    BatchedArena (the Coach's gate) and BatchedPit (any two player kinds), on device
 """

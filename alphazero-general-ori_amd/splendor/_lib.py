@@ -71,6 +71,8 @@ _SIGS = {
                      C.c_uint32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_playout_seq": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp,
                          C.c_uint32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "spl_playout_mix": ([C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp,
+                         C.c_uint32, _vp, _vp, _vp, _vp], C.c_int),
     "spl_mcts_create": ([C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)], C.c_int),
     "spl_mcts_destroy": ([C.c_void_p], C.c_int),
     "spl_mcts_device_bytes": ([C.c_void_p], C.c_longlong),

@@ -16,7 +16,10 @@ plays the self-play of learn()'s first k iterations with the network-free rollou
 (splendor.playout.PlayoutEvaluator on the same trees: uniform priors, leaf values from
 `args.bootstrap_playouts` random playouts under `args.bootstrap_policy`), the usual cold start
 from a random-init network; `use_rollout_selfplay()` is the same switch for callers that drive
-executeIteration themselves and `refresh_network()` the way back.
+executeIteration themselves and `refresh_network()` the way back. `args.rollout_mix` (a float,
+or one lambda per learn() iteration) plays the iterations after the bootstrap with the mixed
+evaluator (splendor.playout.MixedEvaluator: the network's priors, leaf values (1 - lambda)
+v_network + lambda v_playout); `use_mixed_selfplay(lam)` is that switch.
 """
 import numpy as np
 import torch
@@ -25,7 +28,7 @@ from . import _lib
 from .env import unpack_mask
 from .arena import BatchedArena, accept_new_network
 from .examples import ExampleHistory, ExampleSet, LazySymmetryExamples
-from .playout import PlayoutEvaluator
+from .playout import MixedEvaluator, PlayoutEvaluator
 from .search import evaluator_for, nn_precision_arg
 from .selfplay import SelfPlay, gather_examples
 
@@ -60,19 +63,23 @@ class Coach:
         reserve-free tree's. The engine's rules are the same before and after.
         args.bootstrap_iters (default 0: nothing changes anywhere), args.bootstrap_playouts
         (default 4) and args.bootstrap_policy (default "buy_first"): learn()'s first iterations
-        play their self-play with the rollout search (use_rollout_selfplay)."""
+        play their self-play with the rollout search (use_rollout_selfplay).
+        args.rollout_mix (default 0: nothing is built): a float, or a sequence with one lambda
+        per learn() iteration; an iteration after the bootstrap whose lambda is not 0 plays its
+        self-play with the mixed evaluator (use_mixed_selfplay), every other one as before."""
         self.game, self.nnet, self.args = game, nnet, args
         B = int(batch or _arg(args, "numEps", 1))
         self.B = B
         self.seed, self.board_base = seed, board_base
         self.mem_budget = mem_budget
         self._rollout_ev = {}                                # (playouts, policy) -> PlayoutEvaluator
+        self._mixed_ev = {}                                  # (playouts, policy) -> MixedEvaluator
         # args.selfplay_reserve = False: the self-play handle alone is reserve-free (the engine's
         # own rules are put back once it exists); the gate, the pit and check_valid play the
         # full game on the same engine: the reference's "train without, validate with"
         rules = None if _arg(args, "selfplay_reserve", True) else game.engine.rules | _lib.RULE_NO_RESERVE
-        self.sp = SelfPlay(game.engine, B, args,
-                           evaluator=evaluator_for(game.engine, nnet, B, precision=nn_precision_arg(args)),
+        self._net_ev = evaluator_for(game.engine, nnet, B, precision=nn_precision_arg(args))
+        self.sp = SelfPlay(game.engine, B, args, evaluator=self._net_ev,
                            dirichlet_noise=float(_arg(args, "dirichletAlpha", 0.0)) > 0, seed=seed,
                            board_base=board_base, mem_budget=mem_budget, rules=rules)
         self.sp.reset()
@@ -142,8 +149,8 @@ class Coach:
     def refresh_network(self):
         """Re-pack the leaf evaluator after the network's weights changed (the fused kernel
         reads a packed copy)."""
-        self.sp.set_evaluator(evaluator_for(self.game.engine, self.nnet, self.B,
-                                            precision=nn_precision_arg(self.args)))
+        self._net_ev = evaluator_for(self.game.engine, self.nnet, self.B, precision=nn_precision_arg(self.args))
+        self.sp.set_evaluator(self._net_ev)
 
     def use_rollout_selfplay(self, playouts=None, policy=None):
         """Play the following self-play on the same trees with the network-free rollout search:
@@ -163,6 +170,36 @@ class Coach:
         self.sp.set_evaluator(ev)
         return ev
 
+    def use_mixed_selfplay(self, lam, playouts=None, policy=None):
+        """Play the following self-play with the mixed evaluator: the current network's priors and
+        leaf values (1 - lam) v_network + lam v_playout (splendor.playout.MixedEvaluator; playouts
+        per leaf and playout policy default to the bootstrap arguments, as use_rollout_selfplay,
+        on the Coach's seed and board_base and the handle's rules). One evaluator per (playouts,
+        policy) lives as long as the Coach and is given the latest network evaluator, so its call
+        counter keeps advancing across refresh_network(). While it is the handle's evaluator on
+        the current network, another lam only writes the device scalar and the captured graphs
+        stay; otherwise it goes in through set_evaluator. refresh_network() puts the plain network
+        evaluator back. Returns the evaluator."""
+        P = int(playouts if playouts is not None else _arg(self.args, "bootstrap_playouts", 4) or 4)
+        policy = policy or _arg(self.args, "bootstrap_policy", "buy_first") or "buy_first"
+        ev = self._mixed_ev.get((P, policy))
+        if ev is None:
+            ev = self._mixed_ev[P, policy] = MixedEvaluator(self.game.engine, self._net_ev, P, policy, lam=lam,
+                                                            seed=self.seed, board_base=self.board_base,
+                                                            rules=self.sp.rules)
+        ev.lam = lam
+        if self.sp.evaluator is not ev or ev.network is not self._net_ev:
+            ev.set_network(self._net_ev)
+            self.sp.set_evaluator(ev)
+        return ev
+
+    def _mix_lambda(self, i):
+        """args.rollout_mix for learn()'s iteration i (1-based): 0 when absent or past the end."""
+        mix = _arg(self.args, "rollout_mix", 0) or 0
+        if isinstance(mix, (int, float)):
+            return float(mix)
+        return float(mix[i - 1]) if i <= len(mix) else 0.0
+
     def learn(self, pnet=None, log=None):
         """Coach.learn (Coach.py:102-164): for numIters iterations, numEps self-play games
         (fresh games and trees, as the reference's executeEpisode + reset_all_search_trees),
@@ -174,7 +211,8 @@ class Coach:
         checkpoint_<i>.pt / best.pt / temp.pt in args.checkpoint. In iterations i <=
         args.bootstrap_iters the self-play runs on the rollout search (use_rollout_selfplay);
         training, the gate and the checkpoints are the same, and the network evaluator is back
-        after the iteration. Returns per-iteration (nwins, pwins, draws, accepted)."""
+        after the iteration. A later iteration whose args.rollout_mix entry is not 0 plays on the
+        mixed evaluator in the same way (use_mixed_selfplay). Returns per-iteration (nwins, pwins, draws, accepted)."""
         from .NNet import NNetWrapper
         folder = _arg(self.args, "checkpoint", "checkpoint")
         pnet = pnet or NNetWrapper(self.game, dict(self.nnet.args), device=self.nnet.device)
@@ -184,6 +222,8 @@ class Coach:
             if not _arg(self.args, "skipFirstSelfPlay", False) or i > 1:
                 if i <= bootstrap:
                     self.use_rollout_selfplay()
+                elif self._mix_lambda(i) != 0:
+                    self.use_mixed_selfplay(self._mix_lambda(i))
                 self.sp.reset()
                 self.executeIteration(int(_arg(self.args, "numEps", self.B)), gather=True)
             self.saveTrainExamples(folder)

@@ -327,6 +327,37 @@ class SplendorEngine:
                    "spl_playout_seq")
         return out
 
+    def playout_mix(self, state, call_seq, lam, v, active=None, index=None, count=None, policy="buy_first",
+                    playouts=1, max_steps=None, seed=0, board_base=0, unfinished=None):
+        """playout_seq() blended into a value buffer (spl_playout_mix): for every row that runs,
+        v[b] = (1 - l) v[b] + l mean[b] in f32, in place, with the rows, the keys and the mean of
+        playout_seq(call_seq, ...). lam is a one-element f32 device tensor read on the device and
+        clamped to 0..1 there (NaN counts as 0), so a write to it reaches a captured launch; at 0
+        the launch changes nothing. v: f32 [B, n], contiguous (the network's values). Rows that do
+        not run keep every byte of v. Returns (v, unfinished), the counter an int32 [1] that
+        accumulates (`unfinished`: one from an earlier call)."""
+        B, P, dev = state.shape[0], int(playouts), self.device
+        kind = self.PLAYOUT_POLICIES.get(policy, policy)
+        if not isinstance(kind, int):
+            raise ValueError(f"playout_mix: policy must be one of {sorted(self.PLAYOUT_POLICIES)}, got {policy!r}")
+        for t, dt, rows, name in ((state, (torch.int8,), B, "state"), (active, (torch.uint8,), B, "active"),
+                                  (index, (torch.int32,), B, "index"), (count, (torch.int32,), (B + 63) // 64, "count"),
+                                  (call_seq, (torch.int32, torch.uint32), 1, "call_seq"),
+                                  (lam, (torch.float32,), 1, "lam"), (v, (torch.float32,), B, "v")):
+            if t is not None and (t.dtype not in dt or t.shape[0] != rows or not t.is_contiguous()):
+                raise ValueError(f"playout_mix: {name} must be a contiguous {dt[0]} tensor with {rows} rows")
+        if call_seq is None or lam is None or v is None or tuple(v.shape) != (B, self.n):
+            raise ValueError(f"playout_mix: call_seq, lam and v (f32 [{B}, {self.n}]) are required")
+        if (index is None) != (count is None) or (active is not None and index is not None):
+            raise ValueError("playout_mix: index and count go together and exclude active")
+        if unfinished is None:
+            unfinished = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(self.L.spl_playout_mix(self.ctx, B, _ptr(state), _ptr(active), _ptr(index), _ptr(count), kind, P,
+                                          int(62 * self.n if max_steps is None else max_steps), seed, _ptr(call_seq),
+                                          int(board_base), _ptr(lam), _ptr(v), _ptr(unfinished), self._s()),
+                   "spl_playout_mix")
+        return v, unfinished
+
 
 class RolloutBatch:
     """B boards of random-policy self-play, stepped by one fused launch per step

@@ -14,12 +14,16 @@ Player specs (what pit.py's create_player builds from a name):
   playouts (splendor.playout.PlayoutEvaluator, one spl_playout launch per simulation). Its
   strength is set by simulations per move and playouts per leaf: a fixed yardstick between
   the random and the greedy player and beyond;
+* MixedPlayer(nnet, lam, playouts=1, policy="buy_first", numMCTSSims=, cpuct=, fpu=,
+  nn_precision=): a search player seated like MCTSPlayer whose leaves get the network's priors
+  and the value (1 - lam) v_network + lam v_playout (splendor.playout.MixedEvaluator); at lam =
+  0 it moves exactly as MCTSPlayer(nnet);
 * PolicyPlayer(nnet, evaluator=None): the arg-max of the network's policy over the legal
   moves, no search;
 * GreedyPlayer(): SplendorPlayers.py:93-115, scoring the mover (DESIGN.md);
 * RandomPlayer(): SplendorPlayers.py:18-25.
 The last three move by one spl_player_move launch per ply and allocate no tree.
-A RolloutPlayer draws its playouts with its search seed (seed ^ (k + 1)), board = game_base +
+A RolloutPlayer (and a MixedPlayer) draws its playouts with its search seed (seed ^ (k + 1)), board = game_base +
 slot * playouts + playout, streams 256 c .. for its c-th simulation: a run repeats exactly.
 
 Every player follows the engine's rules as they are when the pit is created (after
@@ -35,7 +39,7 @@ import torch
 from . import _lib
 from .arena import BatchedArena, TreePlayer, _arg, arena_mcts_args
 from .mcts import BatchedMCTS
-from .playout import PlayoutEvaluator
+from .playout import MixedEvaluator, PlayoutEvaluator
 from .search import evaluator_for, nn_precision_arg
 
 
@@ -47,6 +51,16 @@ class MCTSPlayer:
 
 class RolloutPlayer:
     def __init__(self, numMCTSSims=None, playouts=1, policy="buy_first", cpuct=None, fpu=None):
+        self.playouts, self.policy = int(playouts), policy
+        self.own = dict(numMCTSSims=numMCTSSims, cpuct=cpuct, fpu=fpu)
+
+
+class MixedPlayer:
+    evaluator = None
+
+    def __init__(self, nnet, lam, playouts=1, policy="buy_first", numMCTSSims=None, cpuct=None, fpu=None,
+                 nn_precision=None):
+        self.nnet, self.lam, self.nn_precision = nnet, MixedEvaluator._check_lam(lam), nn_precision
         self.playouts, self.policy = int(playouts), policy
         self.own = dict(numMCTSSims=numMCTSSims, cpuct=cpuct, fpu=fpu)
 
@@ -105,7 +119,7 @@ class BatchedPit(BatchedArena):
         specs = (player1, player2)
         # the networks first, then the trees share the memory that is left (as BatchedArena)
         evs = [self._evaluator(s) for s in specs]
-        trees = sum(isinstance(s, (MCTSPlayer, RolloutPlayer)) for s in specs)
+        trees = sum(isinstance(s, (MCTSPlayer, RolloutPlayer, MixedPlayer)) for s in specs)
         budget = None
         if trees and mem_budget:
             budget = int(mem_budget) // trees
@@ -117,7 +131,7 @@ class BatchedPit(BatchedArena):
         self.capacity = {"prunes": 0, "resets": 0, "unexpanded": 0}
 
     def _evaluator(self, spec):
-        if not isinstance(spec, (MCTSPlayer, PolicyPlayer)):
+        if not isinstance(spec, (MCTSPlayer, MixedPlayer, PolicyPlayer)):
             return None
         if spec.evaluator is not None:
             return spec.evaluator
@@ -128,7 +142,10 @@ class BatchedPit(BatchedArena):
 
     def _seat(self, k, spec, evaluator, budget):
         seed = self.mcts_seed(k)
-        if isinstance(spec, MCTSPlayer):
+        if isinstance(spec, MixedPlayer):
+            evaluator = MixedEvaluator(self.e, evaluator, spec.playouts, spec.policy, lam=spec.lam, seed=seed,
+                                       board_base=self.game_base)
+        if isinstance(spec, (MCTSPlayer, MixedPlayer)):
             return TreePlayer(BatchedMCTS(self.e, self.B, arena_mcts_args(self.args, **spec.own), evaluator,
                                           dirichlet_noise=False, seed=seed, board_base=self.game_base,
                                           mem_budget=budget))
@@ -141,5 +158,5 @@ class BatchedPit(BatchedArena):
             return PriorPlayer(self.e, evaluator, seed)
         if isinstance(spec, (GreedyPlayer, RandomPlayer)):
             return RulePlayer(self.e, spec.kind, seed)
-        raise TypeError(f"player {k + 1}: expected MCTSPlayer, RolloutPlayer, PolicyPlayer, GreedyPlayer or "
-                        f"RandomPlayer, got {type(spec).__name__}")
+        raise TypeError(f"player {k + 1}: expected MCTSPlayer, RolloutPlayer, MixedPlayer, PolicyPlayer, "
+                        f"GreedyPlayer or RandomPlayer, got {type(spec).__name__}")

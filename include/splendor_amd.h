@@ -261,6 +261,25 @@ int spl_playout_seq(const spl_ctx *ctx, int B, const int8_t *state, const uint8_
                     float *result, float *pi_out, int32_t *steps_out, int32_t *unfinished,
                     void *hip_stream);
 
+/* spl_playout_seq blended into a value buffer (AlphaGo's mixed leaf value): the rows, the task
+ * keys (board id board_base + b P + j, stream base from *call_seq) and each row's f32 mean m (the
+ * sum in ascending j over (float)P) are spl_playout_seq's; instead of storing m, every row b that
+ * runs and every seat i gets
+ *   v[b][i] = (1.0f - l) * v[b][i] + l * m[b][i]
+ * in f32 exactly as written (two products, one sum, no FMA contraction), read and written in
+ * place (v: B x n f32, typically the network's values of the same leaf list). l is *lambda, one
+ * device f32 read when the kernel runs and clamped with fminf(fmaxf(x, 0.f), 1.f) (a NaN counts
+ * as 0): like call_seq it is a pointer so that a host write reaches every later replay of a
+ * captured launch. With l == 0 every workgroup leaves before it stages anything and v is
+ * untouched. Rows that do not run keep every byte of v; there is no pi_out and no steps_out (the
+ * priors stay the caller's); *unfinished accumulates as in spl_playout. SPL_EINVAL before any
+ * launch: as spl_playout_seq, plus NULL lambda or NULL v. B == 0 launches nothing. */
+int spl_playout_mix(const spl_ctx *ctx, int B, const int8_t *state, const uint8_t *active,
+                    const int32_t *leaf_index, const int32_t *leaf_count,
+                    int policy, int playouts, int max_steps, uint64_t seed,
+                    const uint32_t *call_seq, uint32_t board_base,
+                    const float *lambda, float *v, int32_t *unfinished, void *hip_stream);
+
 
 /* ===================================================================== MCTS
  * Device-resident batched PUCT search (MCTS.py), one tree per board/game, B trees.

@@ -6,13 +6,16 @@ over many games at once and print (oneWon, twoWon, draws).
     python3 tools/pit.py -p checkpoint/best.pt greedy -n 4096 -m 100 -c 2.5 -f 0.3 --json out.json
     python3 tools/pit.py -p a.pt a.pt -m1 50 -m2 200              # pit.py's ai_1 / ai_2
     python3 tools/pit.py -p rollout:buy_first:4 greedy -n 1024 -m 100 -c 2.5 -f 0.3
+    python3 tools/pit.py -p mixed:checkpoint/best.pt:0.5:buy_first:4 greedy -n 1024 -m 100 -c 2.5 -f 0.3
 
 A player is `random`, `greedy` (SplendorPlayers.py), a checkpoint path (search with -m / -c /
 -f, as pit.py's create_player), `policy:<checkpoint>` (the network's arg-max policy, no
 search), `init` / `policy:init` (the seeded random-init network, a floor for trained
 ones), or `rollout` / `rollout:<policy>:<playouts>` (the search without a network: uniform
 priors, leaf values from <playouts> random playouts, policy uniform or buy_first; default
-buy_first:1; simulations from -m / -m1 / -m2). Checkpoints load through NNetWrapper.load_checkpoint (weights only). Every game is
+buy_first:1; simulations from -m / -m1 / -m2), or `mixed:<checkpoint>:<lambda>` /
+`mixed:<checkpoint>:<lambda>:<policy>:<playouts>` (the checkpoint's search with leaf values (1 -
+lambda) v_network + lambda v_playout; default buy_first:1). Checkpoints load through NNetWrapper.load_checkpoint (weights only). Every game is
 played on the device (splendor.pit.BatchedPit): --batch games at a time, Philox-keyed by
 --seed, so a run repeats exactly. --no-reserve plays the reserve-free game (actions 12..26
 never legal, the reference's training-time rule) for both players. --json appends the run's record (players, settings,
@@ -42,8 +45,14 @@ def create_player(name, game, sims, cpuct, fpu):
             raise SystemExit(f"{name}: expected rollout or rollout:<policy>:<playouts>")
         kw = dict(policy=part[1], playouts=int(part[2])) if len(part) == 3 else {}
         return pit.RolloutPlayer(numMCTSSims=sims, cpuct=cpuct, fpu=fpu, **kw)
-    policy = name.startswith("policy:")
+    policy, mixed = name.startswith("policy:"), name.startswith("mixed:")
     path = name[len("policy:"):] if policy else name
+    if mixed:
+        part = name.split(":")
+        if len(part) not in (3, 5):
+            raise SystemExit(f"{name}: expected mixed:<checkpoint>:<lambda>[:<policy>:<playouts>]")
+        path, lam = part[1], float(part[2])
+        kw = dict(policy=part[3], playouts=int(part[4])) if len(part) == 5 else {}
     if os.path.isdir(path):
         path = os.path.join(path, "best.pt")                 # pit.py:97
     net = NNetWrapper(game, dict(dropout=0.0), seed=0)
@@ -51,6 +60,8 @@ def create_player(name, game, sims, cpuct, fpu):
         net.load_checkpoint(*os.path.split(path))
     if policy:
         return pit.PolicyPlayer(net)
+    if mixed:
+        return pit.MixedPlayer(net, lam, numMCTSSims=sims, cpuct=cpuct, fpu=fpu, **kw)
     return pit.MCTSPlayer(net, numMCTSSims=sims, cpuct=cpuct, fpu=fpu)
 
 

@@ -18,7 +18,13 @@ by segment as spl_mcts_select_compact lists leaves; the two launches alternate i
 --mode iteration: ms per self-play iteration (select, playouts, backup, commit) of SelfPlay at
 --boards games with the rollout evaluator (--playouts, buy-first) at config 3's search
 arguments, eager and as replayed graphs, over --iters iterations after --stagger warm-up
-iterations, with the window's capacity events. Both print one JSON record and write it to --out.
+iterations, with the window's capacity events.
+--mode mix: spl_playout_mix (lambda 0.5) against spl_playout_seq on the same leaf list, and the
+lambda = 0 launch (empty workgroups), alternating in one process; the blend is compared with the
+host formula over spl_playout_seq's means first.
+--mode mix-iteration: --mode iteration for the network evaluator (seeded random-init network),
+the rollout evaluator and the mixed evaluator (lambda 0.5) on three handles in one process.
+Every mode prints one JSON record and writes it to --out.
 """
 import argparse
 import json
@@ -47,9 +53,11 @@ def summary(us):
             "p90_us": round(float(np.percentile(us, 90)), 1), "launches": int(len(us))}
 
 
-def list_mode(a):
+def listed_leaves(a):
+    """The mid-game canonical boards and a seeded --share of them as flags and as the segmented
+    leaf list -> (engine, boards, listed, flags, index, count, moves from the deal)."""
     from splendor.env import RolloutBatch, SplendorEngine
-    n, B, P = a.players, a.boards, a.playouts
+    n, B = a.players, a.boards
     e = SplendorEngine(n, device="cuda:0")
     dev = e.device
     rb = RolloutBatch(e, B, seed=a.seed)
@@ -64,8 +72,13 @@ def list_mode(a):
         index[64 * j:64 * j + len(rows)] = rows
         count[j] = len(rows)
     flags = torch.from_numpy(listed.astype(np.uint8)).to(dev)
-    index, count = torch.from_numpy(index).to(dev), torch.from_numpy(count).to(dev)
-    seq = torch.tensor([5], dtype=torch.int32, device=dev)
+    return e, st, listed, flags, torch.from_numpy(index).to(dev), torch.from_numpy(count).to(dev), moves
+
+
+def list_mode(a):
+    n, B, P = a.players, a.boards, a.playouts
+    e, st, listed, flags, index, count, moves = listed_leaves(a)
+    seq = torch.tensor([5], dtype=torch.int32, device=e.device)
     kw = dict(policy="buy_first", playouts=P, seed=a.seed, pi=True)
     o_flag = e.playout(st, active=flags, step0=5 * 256, **kw)
     o_list = e.playout_seq(st, seq, index=index, count=count, **kw)
@@ -89,10 +102,42 @@ def list_mode(a):
     return rec
 
 
-def iteration_mode(a):
-    import time
+def mix_mode(a):
+    n, B, P = a.players, a.boards, a.playouts
+    e, st, listed, flags, index, count, moves = listed_leaves(a)
+    dev = e.device
+    seq = torch.tensor([5], dtype=torch.int32, device=dev)
+    kw = dict(index=index, count=count, policy="buy_first", playouts=P, seed=a.seed)
+    v0 = torch.from_numpy(np.random.default_rng(a.seed).random((B, n), dtype=np.float32) * 2 - 1).to(dev)
+    half, zero = (torch.tensor([x], dtype=torch.float32, device=dev) for x in (0.5, 0.0))
+    o_seq = e.playout_seq(st, seq, **kw)
+    v, unfinished = e.playout_mix(st, seq, half, v0.clone(), **kw)
+    vz, _ = e.playout_mix(st, seq, zero, v0.clone(), **kw)
+    torch.cuda.synchronize()
+    want = np.where(listed[:, None], np.float32(0.5) * v0.cpu().numpy() + np.float32(0.5) * o_seq["result"].cpu().numpy(),
+                    v0.cpu().numpy())
+    assert np.array_equal(v.cpu().numpy(), want) and torch.equal(vz, v0) and int(unfinished.item()) == 0
+    runs = {"playout_seq_list": lambda: e.playout_seq(st, seq, out=o_seq, **kw),
+            "playout_mix_list": lambda: e.playout_mix(st, seq, half, v, unfinished=unfinished, **kw),
+            "playout_mix_lambda0": lambda: e.playout_mix(st, seq, zero, vz, unfinished=unfinished, **kw)}
+    times = {k: [] for k in runs}
+    for rep in range(a.warmup + a.reps):
+        for k, fn in runs.items():
+            t = timed(fn)
+            if rep >= a.warmup:
+                times[k].append(t)
+    rec = {"mode": "mix", "players": n, "boards": B, "playouts": P, "policy": "buy_first", "moves_from_deal": moves,
+           "seed": a.seed, "share": a.share, "listed": int(listed.sum()), "blend_equals_host_formula": True}
+    rec.update({k: summary(t) for k, t in times.items()})
+    s = rec["playout_seq_list"]
+    rec["mix_over_seq"] = round(rec["playout_mix_list"]["median_us"] / s["median_us"], 3)
+    rec["mix_inside_seq_p10_p90"] = bool(s["p10_us"] <= rec["playout_mix_list"]["median_us"] <= s["p90_us"])
+    return rec
+
+
+def iteration_mode(a, mixed=False):
     from splendor.env import SplendorEngine
-    from splendor.playout import PlayoutEvaluator
+    from splendor.playout import MixedEvaluator, PlayoutEvaluator
     from splendor.selfplay import SelfPlay
     n, B, P = a.players, a.boards, a.playouts
     e = SplendorEngine(n, device="cuda:0")
@@ -100,8 +145,30 @@ def iteration_mode(a):
                 dirichletAlpha=0.3, temperature=[1.25, 0.8], tempThreshold=10)
     rec = {"mode": "iteration", "players": n, "games": B, "playouts": P, "policy": "buy_first", "args": args,
            "stagger_iterations": a.stagger, "iterations": a.iters}
+    if mixed:
+        from splendor.nnet import LeafEvaluator, random_net
+        rec["mode"] = "mix-iteration"
+        net = random_net(n, seed=0, device="cuda:0")
+        for name, make in (("network", lambda: LeafEvaluator(e, net, B, use_graph=False)),
+                           ("rollout", lambda: PlayoutEvaluator(e, P, "buy_first", seed=a.seed)),
+                           ("mixed", lambda: MixedEvaluator(e, LeafEvaluator(e, net, B, use_graph=False), P,
+                                                            "buy_first", lam=0.5, seed=a.seed))):
+            sp = SelfPlay(e, B, args, evaluator=make(), dirichlet_noise=True, seed=a.seed,
+                          mem_budget=int(0.25 * torch.cuda.mem_get_info()[0]))
+            rec[name] = time_iterations(a, sp)
+            del sp
+        return rec
     sp = SelfPlay(e, B, args, evaluator=PlayoutEvaluator(e, P, "buy_first", seed=a.seed), dirichlet_noise=True,
                   seed=a.seed)
+    rec.update(time_iterations(a, sp))
+    rec["evaluator_calls"] = sp.evaluator.calls
+    return rec
+
+
+def time_iterations(a, sp):
+    """ms per iteration of one handle, graphed then eager, after the warm-up."""
+    import time
+    rec = {}
     sp.reset()
     sp.run(a.stagger, use_graph=True)
     sp.drain(allow_drops=True)
@@ -120,7 +187,6 @@ def iteration_mode(a):
         rec[name] = {"ms_per_iteration": round(dt / a.iters * 1e3, 4), "simulations_per_s": d["sims_backed"] / dt,
                      "moves": d["moves"], "games_done": d["games_done"],
                      "capacity_events": {k: d[k] for k in ("prunes", "resets", "unexpanded")}}
-    rec["evaluator_calls"] = sp.evaluator.calls
     return rec
 
 
@@ -134,13 +200,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0x5EED)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "playout.json"))
-    ap.add_argument("--mode", choices=("launch", "list", "iteration"), default="launch")
+    ap.add_argument("--mode", choices=("launch", "list", "iteration", "mix", "mix-iteration"), default="launch")
     ap.add_argument("--share", type=float, default=0.69, help="list mode: share of the boards that is listed")
     ap.add_argument("--iters", type=int, default=2000, help="iteration mode: timed iterations per variant")
     ap.add_argument("--stagger", type=int, default=600, help="iteration mode: warm-up iterations")
     a = ap.parse_args()
     if a.mode != "launch":
-        rec = (list_mode if a.mode == "list" else iteration_mode)(a)
+        rec = {"list": list_mode, "iteration": iteration_mode, "mix": mix_mode,
+               "mix-iteration": lambda a: iteration_mode(a, mixed=True)}[a.mode](a)
         print(json.dumps(rec, indent=1), flush=True)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

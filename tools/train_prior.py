@@ -6,13 +6,16 @@ concurrent trees, training on the example history (GenericNNetWrapper.train's lo
 schedule, larger batches), the BatchedArena gate against the previous weights. Writes the
 accepted weights as a plain state_dict checkpoint ({"state_dict": ...}, weights-only loadable)
 and one JSON line per iteration (losses, arena result, self-play figures) to stdout:
-    python3 tools/train_prior.py OUT.pt [iterations] [games] [no-reserve] [bootstrap=K[:P]]
+    python3 tools/train_prior.py OUT.pt [iterations] [games] [no-reserve] [bootstrap=K[:P]] [mix=L1,L2,..[:P]]
 bench.py --net OUT.pt then runs the headline on these weights. A fourth argument `no-reserve`
 plays the self-play games without the reserve moves 12..26 (args.selfplay_reserve = False,
 the reference's training recipe); the arena gate still plays the full game. `bootstrap=K[:P]`
 (anywhere after OUT.pt) plays the self-play of the first K iterations with the network-free
 rollout search, P buy-first playouts per leaf (default 4; Coach.use_rollout_selfplay), on the
-same trees and search arguments; every iteration's line names the evaluator that played it."""
+same trees and search arguments. `mix=L1,L2,...[:P]` plays iteration i (after the bootstrap) with
+the mixed evaluator when Li is not 0: the network's priors, leaf values (1 - Li) v_network + Li
+v_playout from P buy-first playouts (default 4; Coach.use_mixed_selfplay); iterations past the
+list play on the network. Every iteration's line names the evaluator that played it."""
 import json
 import os
 import re
@@ -34,6 +37,13 @@ for arg in [x for x in sys.argv[1:] if x.startswith("bootstrap=")]:
     if not m:
         raise SystemExit(f"{arg}: expected bootstrap=ITERATIONS[:PLAYOUTS]")
     bootstrap_iters, bootstrap_playouts = int(m.group(1)), int(m.group(2) or 4)
+    sys.argv.remove(arg)
+mix, mix_playouts = [], 4
+for arg in [x for x in sys.argv[1:] if x.startswith("mix=")]:
+    m = re.fullmatch(r"mix=([0-9.,]+)(?::(\d+))?", arg)
+    if not m:
+        raise SystemExit(f"{arg}: expected mix=LAMBDA,LAMBDA,...[:PLAYOUTS]")
+    mix, mix_playouts = [float(x) for x in m.group(1).split(",")], int(m.group(2) or 4)
     sys.argv.remove(arg)
 out = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/trained_2p.pt"
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -71,6 +81,9 @@ for i in range(1, iters + 1):
     if i <= bootstrap_iters:                                # (learn() puts the network back afterwards)
         ev = coach.use_rollout_selfplay(playouts=bootstrap_playouts)
         played = f"rollout:{ev.policy}:{ev.playouts}"
+    elif i <= len(mix) and mix[i - 1] != 0:
+        ev = coach.use_mixed_selfplay(mix[i - 1], playouts=mix_playouts)
+        played = f"mixed:{ev.lam}:{ev.policy}:{ev.playouts}"
     (nw, pw, dr, ok), = coach.learn(pnet=pnet)
     accepted += bool(ok)
     st = coach.sp.stats()
@@ -81,4 +94,4 @@ for i in range(1, iters + 1):
 os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
 torch.save({"state_dict": nn.nnet.state_dict(), "iterations": iters, "accepted": accepted}, out)
 print(json.dumps({"saved": out, "iterations": iters, "accepted": accepted, "bootstrap_iters": bootstrap_iters,
-                  "bootstrap_playouts": bootstrap_playouts}), flush=True)
+                  "bootstrap_playouts": bootstrap_playouts, "mix": mix, "mix_playouts": mix_playouts}), flush=True)
