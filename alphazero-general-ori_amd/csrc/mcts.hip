@@ -3141,6 +3141,79 @@ __global__ __launch_bounds__(THREADS) void k_root_stats(Pools P, SearchCfg C, in
     }
 }
 
+// principal variations (spl_mcts_pv): per tree `lines` walks of at most `depth` levels along the
+// most visited edges, read-only. At each node the lanes stride over its visit block and reduce
+// the key (Nsa << 16) | (0xFFFF - action): (Nsa descending, action ascending), unique within a
+// node; root line k takes the largest key below line k - 1's. A dependent chain of loads per
+// wave: a diagnostic, not a hot kernel. Each lane writes only its own entries (lane 0 the
+// levels walked, the lanes together the fill past the line's end), so no store is ordered
+// against another lane's.
+__global__ __launch_bounds__(THREADS) void k_pv(Pools P, int B, int lines, int depth, int16_t *action,
+                                                int32_t *visits, double *q, float *prior,
+                                                int32_t *length, uint8_t *end) {
+    const int w = threadIdx.x >> 6, t = blockIdx.x * WAVES + w;
+    if (t >= B) return;
+    const int l = lane_id();
+    const int nlim = P.npages * NPG;
+    const int64_t ulim = (int64_t)P.epages * UPG;
+    // (a handle that was never rooted has zeroed headers: root 0 with no node stored)
+    const int root = P.hdr[t].node_count > 0 ? P.hdr[t].root : -1;
+    uint64_t prev = ~0ull;                                    // the previous line's root key
+    for (int k = 0; k < lines; k++) {
+        const size_t o = ((size_t)t * lines + k) * depth;
+        int len = 0, code = SPL_PV_END_NONE;
+        int node = root >= 0 && root < nlim ? root : -1;
+        while (node >= 0) {
+            const NodeCold c = P.nd[node].c;
+            const int64_t vb = c.vb();
+            int vcnt = min(c.vcnt(), SPL_ACTIONS);
+            if (vb + (int64_t)REC_UNITS * vcnt > ulim) vcnt = 0;   // (never read past the pool)
+            uint64_t best = 0;
+            int bi = -1;
+            for (int i = l; i < vcnt; i += 64) {
+                const VisitRec r = *P.vr(vb + (int64_t)REC_UNITS * i);
+                if (r.n < 1) continue;
+                const uint64_t key = ((uint64_t)(uint32_t)r.n << 16) | (uint64_t)(0xFFFF - (int)(uint16_t)r.a);
+                if ((len > 0 || key < prev) && key > best) { best = key; bi = i; }
+            }
+            uint64_t top = best;
+            for (int s = 32; s > 0; s >>= 1) {
+                const uint64_t x = __shfl_xor(top, s, 64);
+                top = x > top ? x : top;
+            }
+            if (top == 0) {                                   // no (further) visited edge here
+                if (len > 0) code = SPL_PV_END_UNVISITED;
+                break;
+            }
+            const int src = __ffsll((unsigned long long)__ballot(best == top)) - 1;
+            const VisitRec r = *P.vr(vb + (int64_t)REC_UNITS * __shfl(bi, src, 64));
+            if (l == 0) {
+                action[o + len] = r.a;
+                if (visits) visits[o + len] = r.n;
+                if (q) q[o + len] = r.q;
+                if (prior)
+                    prior[o + len] = r.off >= 0 && r.off < c.ec && c.eb() + r.off < ulim ? P.ep(c.eb() + r.off)->p : r.p;
+            }
+            if (len == 0) prev = top;
+            len++;
+            if (len == depth) { code = SPL_PV_END_DEPTH; break; }
+            if (r.child < 0 || r.child >= nlim) { code = SPL_PV_END_UNLINKED; break; }
+            if (P.nd[r.child].h.term) { code = SPL_PV_END_TERMINAL; break; }
+            node = r.child;
+        }
+        for (int d = len + l; d < depth; d += 64) {
+            action[o + d] = -1;
+            if (visits) visits[o + d] = 0;
+            if (q) q[o + d] = Q_UNSET;
+            if (prior) prior[o + d] = 0.f;
+        }
+        if (l == 0) {
+            length[(size_t)t * lines + k] = len;
+            if (end) end[(size_t)t * lines + k] = (uint8_t)code;
+        }
+    }
+}
+
 // root priors Ps as stored (MCTS.py:147/176), 409 floats per tree
 __global__ __launch_bounds__(THREADS) void k_root_priors(Pools P, int B, float *ps) {
     const int w = threadIdx.x >> 6, t = blockIdx.x * WAVES + w;
@@ -3657,6 +3730,16 @@ int spl_mcts_root_stats(spl_mcts *m, int64_t *counts, double *qsa, double *probs
     if (!m) return SPL_EINVAL;
     hipLaunchKernelGGL(k_root_stats, wave_grid(m->B), dim3(THREADS), 0, (hipStream_t)hs, m->P,
                        m->cfg, m->B, m->n, counts, qsa, probs, q, adjusted);
+    return check_launch();
+}
+
+int spl_mcts_pv(spl_mcts *m, int lines, int depth, int16_t *action, int32_t *visits, double *q,
+                float *prior, int32_t *length, uint8_t *end, void *hs) {
+    if (!m || !action || !length || lines < 1 || lines > SPL_PV_MAX_LINES || depth < 1 ||
+        depth > SPL_PV_MAX_DEPTH)
+        return SPL_EINVAL;
+    hipLaunchKernelGGL(k_pv, wave_grid(m->B), dim3(THREADS), 0, (hipStream_t)hs, m->P, m->B, lines, depth,
+                       action, visits, q, prior, length, end);
     return check_launch();
 }
 

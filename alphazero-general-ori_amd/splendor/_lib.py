@@ -17,6 +17,9 @@ BACKUP_DEFER_GC = 4              # spl_mcts_backup_kind: SPL_BACKUP_DEFER_GC
 PLAYER_RANDOM, PLAYER_GREEDY, PLAYER_POLICY = 0, 1, 2   # spl_player_move: SPL_PLAYER_*
 PLAYOUT_UNIFORM, PLAYOUT_BUY_FIRST = 0, 1               # spl_playout: SPL_PLAYOUT_*
 RULE_NO_RESERVE = 1                                     # spl_ctx_set_rules: SPL_RULE_NO_RESERVE
+PV_MAX_LINES, PV_MAX_DEPTH = 16, 64                     # spl_mcts_pv: SPL_PV_MAX_*
+PV_END_DEPTH, PV_END_UNLINKED, PV_END_TERMINAL, PV_END_UNVISITED, PV_END_NONE = 0, 1, 2, 3, 4   # SPL_PV_END_*
+Q_UNSET = -42.0                                         # an unvisited edge's Qsa (root_stats, pv)
 
 
 class NativeEngineMissing(RuntimeError):
@@ -89,6 +92,7 @@ _SIGS = {
     "spl_mcts_backup_kind": ([C.c_void_p, _vp, _vp, _vp, C.c_int, _vp], C.c_int),
     "spl_mcts_root_stats": ([C.c_void_p, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_mcts_root_priors": ([C.c_void_p, _vp, _vp], C.c_int),
+    "spl_mcts_pv": ([C.c_void_p, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "spl_mcts_headers": ([C.c_void_p, _vp, _vp], C.c_int),
     "spl_mcts_tree_sizes": ([C.c_void_p, _vp, _vp], C.c_int),
     "spl_mcts_reset_games": ([C.c_void_p, _vp], C.c_int),

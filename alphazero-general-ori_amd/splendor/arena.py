@@ -216,6 +216,18 @@ class BatchedArena:
         self.last = last
         return one, two, int(len(r0) - one - two)
 
+    def record(self):
+        """The last playGames as a replayable record (splendor.review.replay): a copy of
+        `.last` plus the keys of its deals and chance — seed, game_base (game g draws with the
+        Philox board id game_base + g whatever the batch size was), n, and the engine's rules
+        word and token_limit as they are now (they do not change while the arena lives)."""
+        if self.last is None:
+            raise ValueError("record(): no games played yet")
+        rec = {k: np.array(v) for k, v in self.last.items()}
+        rec.update(seed=np.uint64(self.seed), game_base=np.int64(self.game_base), n=np.int32(self.n),
+                   rules=np.int32(self.e.rules), token_limit=np.int32(self.e.token_limit))
+        return rec
+
 
 class Arena:
     """The reference's sequential Arena (Arena.py:15-227) over the engine-backed Game API:

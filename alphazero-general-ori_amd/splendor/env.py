@@ -64,6 +64,7 @@ class SplendorEngine:
         h = C.c_void_p()
         _lib.check(self.L.spl_ctx_create(self.n, int(token_limit), C.byref(h)), "spl_ctx_create")
         self.ctx = h
+        self.token_limit = int(token_limit)
         self.rows = observation_rows(self.n)
         self.S = 7 * self.rows
 
@@ -160,6 +161,7 @@ class SplendorEngine:
     def set_token_limit(self, n):
         """Board.setNumTokenLim (SplendorLogicNumba.py:214-215)."""
         _lib.check(self.L.spl_ctx_set_token_limit(self.ctx, int(n)), "spl_ctx_set_token_limit")
+        self.token_limit = int(n)
 
     @property
     def rules(self):

@@ -344,6 +344,26 @@ class BatchedMCTS:
         _lib.check(self.L.spl_mcts_root_priors(self.h, _ptr(ps), self.e._s()), "spl_mcts_root_priors")
         return ps
 
+    def principal_variations(self, lines=1, depth=8):
+        """The `lines` most visited root edges of every tree, each followed along the most
+        visited edge of every node below it for at most `depth` moves (spl_mcts_pv; order:
+        raw Nsa descending, action ascending). A read-only walk of the stored trees: nothing
+        is re-rooted or collected. -> dict of device tensors: action int16, visits int32, q f64
+        (Qsa for the mover at that node), prior f32, all [B, lines, depth]; length int32 and
+        end uint8 (_lib.PV_END_*), both [B, lines]. Entries past a line's length hold action
+        -1, visits 0, q -42, prior 0."""
+        B, dev, shape = self.B, self.e.device, (self.B, int(lines), int(depth))
+        out = {"action": torch.empty(shape, dtype=torch.int16, device=dev),
+               "visits": torch.empty(shape, dtype=torch.int32, device=dev),
+               "q": torch.empty(shape, dtype=torch.float64, device=dev),
+               "prior": torch.empty(shape, dtype=torch.float32, device=dev),
+               "length": torch.empty((B, int(lines)), dtype=torch.int32, device=dev),
+               "end": torch.empty((B, int(lines)), dtype=torch.uint8, device=dev)}
+        _lib.check(self.L.spl_mcts_pv(self.h, int(lines), int(depth), _ptr(out["action"]), _ptr(out["visits"]),
+                                      _ptr(out["q"]), _ptr(out["prior"]), _ptr(out["length"]), _ptr(out["end"]),
+                                      self.e._s()), "spl_mcts_pv")
+        return out
+
     # ---------------------------------------------------------------- reference API
     def get_action_prob(self, canonical_boards, force_full_search=True, keep_tree=True):
         """Batched MCTS.getActionProb(temp=1) (MCTS.py:45-97): returns (probs f64 [B,409],

@@ -390,6 +390,40 @@ int spl_mcts_backup_kind(spl_mcts *m, const uint64_t *leaf_mask, const float *pi
 int spl_mcts_root_priors(spl_mcts *m, float *ps, void *hip_stream);
 int spl_mcts_root_stats(spl_mcts *m, int64_t *counts, double *qsa, double *probs, double *q,
                         int64_t *adjusted, void *hip_stream);
+/* Principal variations: a read-only walk of the stored trees, `lines` lines of at most `depth`
+ * moves per tree (what the search expects after the move, without re-rooting, which would
+ * collect the rest of the tree). Order a node's edges that have a visit record (Nsa >= 1) by
+ * (Nsa descending, action ascending): the raw counts, not the forced-playout-pruned ones. Line k
+ * (0-based) of tree t starts with the k-th root edge in that order; every level below the root
+ * takes the first edge in that order at the node reached through the previous edge's stored
+ * link. Entry (t, k, d) of action / visits / q / prior (B x lines x depth each) is that edge's
+ * action, Nsa, Qsa and stored prior: Qsa is the f64 as stored, the value for the mover at that
+ * node (canonical seat 0 of that node); the prior is the noised one at a root that was noised
+ * (what spl_mcts_root_priors returns). After a level is written the walk ends with the first of
+ * these that applies, in this order, written to end[t][k] (B x lines u8):
+ *   DEPTH      the line is `depth` moves long;
+ *   UNLINKED   the last edge's child is not stored / not linked (-1, or a link outside the
+ *              node pool, which is never dereferenced);
+ *   TERMINAL   the last edge's child is a terminal node;
+ *   UNVISITED  the child is expanded but has no edge with Nsa >= 1;
+ * and a tree without a root, or with fewer than k + 1 visited root edges, gives NONE. length[t][k]
+ * (B x lines i32) is the number of levels written (0 for NONE). The kernel writes every entry:
+ * those at and past `length` get action -1, visits 0, q -42.0 (root_stats' unvisited qsa) and
+ * prior 0. A line cannot cycle (a child's round is above its parent's); `depth` bounds the walk
+ * regardless. One launch, one wave per tree, loads only; valid whenever spl_mcts_root_stats is,
+ * and nothing in the handle changes. action and length are required, visits / q / prior / end
+ * may be NULL. SPL_EINVAL before any launch: NULL m / action / length, lines outside
+ * 1..SPL_PV_MAX_LINES, depth outside 1..SPL_PV_MAX_DEPTH. */
+#define SPL_PV_MAX_LINES 16
+#define SPL_PV_MAX_DEPTH 64
+#define SPL_PV_END_DEPTH     0
+#define SPL_PV_END_UNLINKED  1
+#define SPL_PV_END_TERMINAL  2
+#define SPL_PV_END_UNVISITED 3
+#define SPL_PV_END_NONE      4
+int spl_mcts_pv(spl_mcts *m, int lines, int depth,
+                int16_t *action, int32_t *visits, double *q, float *prior,
+                int32_t *length, uint8_t *end, void *hip_stream);
 /* ---- self-play (Coach.executeEpisode, Coach.py:50-100), selfplay=1 only ----
  * reset_games: deal B new games (Board.init_game via Philox) and start their searches.
  * commit: for every tree whose search budget is spent, play the move on device:

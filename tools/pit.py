@@ -19,7 +19,8 @@ lambda) v_network + lambda v_playout; default buy_first:1). Checkpoints load thr
 played on the device (splendor.pit.BatchedPit): --batch games at a time, Philox-keyed by
 --seed, so a run repeats exactly. --no-reserve plays the reserve-free game (actions 12..26
 never legal, the reference's training-time rule) for both players. --json appends the run's record (players, settings,
-wins / losses / draws, mean plies, wall seconds) to the JSON list in that file. The human and
+wins / losses / draws, mean plies, wall seconds) to the JSON list in that file. --record FILE.npz saves every game
+move for move (BatchedPit.record() plus the player specs and search arguments) for tools/review.py. The human and
 alpha-beta players, ratings and the board display of pit.py are out of scope."""
 import argparse
 import json
@@ -81,6 +82,8 @@ def main(argv=None):
     ap.add_argument("--no-reserve", action="store_true",
                     help="play without the reserve moves 12..26 (SplendorGame.disableReserve)")
     ap.add_argument("--json", default=None, metavar="FILE", help="append the run's record to this JSON list")
+    ap.add_argument("--record", default=None, metavar="FILE.npz",
+                    help="save the games (every move, with the deal and chance keys) for tools/review.py")
     a = ap.parse_args(argv)
 
     import torch
@@ -105,6 +108,15 @@ def main(argv=None):
            "draws": draws, "mean_plies": float(pit.last["plies"].mean()), "seconds": seconds,
            "capacity_events": pit.capacity}
     print(json.dumps(rec), flush=True)
+    if a.record:
+        # BatchedPit.record() (what splendor.review.replay needs) + who played and how they searched
+        import numpy as np
+        os.makedirs(os.path.dirname(os.path.abspath(a.record)), exist_ok=True)
+        none = float("nan")
+        np.savez_compressed(a.record, **pit.record(), players=np.array(a.players),
+                            numMCTSSims=np.array([-1 if s is None else s for s in sims], dtype=np.int64),
+                            cpuct=np.float64(none if a.cpuct is None else a.cpuct),
+                            fpu=np.float64(none if a.fpu is None else a.fpu))
     if a.json:
         runs = []
         if os.path.exists(a.json):
